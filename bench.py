@@ -2,17 +2,26 @@
 """
 bench.py -- POCS iterations/s (BASELINE.json metric) on N MI355X GPUs.
 
-    python bench.py [--gpus 1] [--steps K] [--warmup W] [--config {0,1,2,3,4}] [--repeats R] [--density M] [--only-main]
+    python bench.py [--gpus 1] [--steps K] [--warmup W] [--config {0,1,2,3,4}] [--repeats R] [--density M] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A "step" is one POCS iteration of the whole cube: every (iline, xline) slice goes once through forward transform ->
 threshold -> inverse transform -> re-insertion of the observed traces -> cost sum.  The timed region is one complete job of K
 iterations on a cube already resident in HBM: statistics of transform(x_obs), threshold schedule (host, a few scalars per
-slice), the K iterations, final store of the result.  The job is repeated R (>= 3) times; `value` is K / the MEDIAN job time
-(max over ranks per repeat), min and max are printed beside it.  For N > 1 the slice axis is cut into N contiguous blocks,
-one rank per GPU; there is no collective inside the timed region -- the blocks are gathered afterwards with one RCCL collective
-on device tensors (all_gather, and gather-to-root beside it; both timed, "gather_ms").  Rank 0 prints ONE JSON line.
+slice), the K iterations, final store of the result.  A plain run times ONE such job after a warm-up job of W iterations, so
+that K steps are timed; `--repeats R` times R jobs, `--full` as many as fill ~1.5 s (R >= 3).  `value` is K / the MEDIAN job
+time (max over ranks per repeat), `ms_per_step` its inverse in milliseconds.  For N > 1 the slice axis is cut into N
+contiguous blocks, one rank per GPU; there is no collective inside the timed region (--full: the blocks are gathered afterwards
+with one RCCL collective on device tensors, all_gather and gather-to-root beside it, both timed, "gather_ms").  Rank 0 prints
+ONE JSON line.
+
+A plain run does nothing but the headline: set up, warm up, time, dump (--dump-outputs), print.  Everything described below
+(CPU baseline and parity, roofline profile, side runs, end to end, other configurations, gather) runs with --full only.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed job computed: `result.npy` (a fixed, seeded sample of the
+slices of rank 0's result cube, at most 48 MiB; complex slices as float32 (..., 2) = real, imaginary) and `iterations_done.npy`
+(float64, iterations run per slice of rank 0's block).  The inputs depend on the arguments only.
 
 --config selects the BASELINE.json configuration of the line's `value` (default 2 = the metric's cube):
     0  64 x 64 x 128 complex64, 50 % missing, FFT, hard, 20 iterations
@@ -25,7 +34,7 @@ on device tensors (all_gather, and gather-to-root beside it; both timed, "gather
        100-iteration schedule, and scales the rate by sample / cube.  `--nslices 1024` runs the whole cube.
 --steps overrides the iteration count of the line's configuration (the driver runs --steps 20).
 
-The default line (config 2) also carries `other_configs`: configs[1], [3] and [4] (N > 1: configs[4] only -- it is the other
+With --full, the default line (config 2) also carries `other_configs`: configs[1], [3] and [4] (N > 1: configs[4] only -- it is the other
 configuration BASELINE.json defines on 8 GPUs) run in the same process at their OWN iteration counts, each with value,
 steady-state rate and a `roofline` object whose launch_ms and algorithmic_bytes_per_launch let the fraction be recomputed; and
 `end_to_end`: the same job through the host-buffer entry point (NumPy cube in, NumPy cube out: PCIe both ways, chunk pipeline).
@@ -85,7 +94,12 @@ def parse_args():
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json configs[i] (default: the metric's cube)")
     ap.add_argument("--steps", type=int, default=None, help="POCS iterations in the timed job (default: the configuration's)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=0, help="timed repeats of the job (0: as many as fill ~1.5 s, between 3 and 15)")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="timed repeats of the job (0: one job of --steps iterations; with --full as many as fill ~1.5 s, between 3 and 15)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: CPU baseline and parity, roofline profile, side runs, end to end, other configurations, gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed job, write what it computed to DIR/<name>.npy (float32 / float64; a fixed sample of the result's slices)")
     ap.add_argument("--nil", type=int, default=None)
     ap.add_argument("--nxl", type=int, default=None)
     ap.add_argument("--nslices", type=int, default=None, help="slices worked on by all GPUs together (config 4: the sample of the cube)")
@@ -103,7 +117,11 @@ def parse_args():
     ap.add_argument("--no-dense", action="store_true", help="skip the side runs (sparse shortcut off, real cube, density curve)")
     ap.add_argument("--only-main", action="store_true", help="no other_configs, no end_to_end (profiling runs)")
     ap.add_argument("--no-end-to-end", action="store_true")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run times the headline job and nothing else
+        args.no_cpu_baseline = args.no_profile = args.no_dense = args.only_main = args.no_end_to_end = True
+    return args
 
 
 def kernel_source_hash():
@@ -379,6 +397,28 @@ def cpu_baseline_shearlet(x, mask, psi, op, nslices_cube, niter=2):
     }, res
 
 
+DUMP_BYTES = 48 << 20    # --dump-outputs: at most this much of the result cube
+
+
+def dump_outputs(dirname, out, done):
+    """DIR/result.npy: a fixed, seeded sample of the slices of the device cube `out` (complex as float32 (..., 2) = real, imaginary; the
+    rows of a slice sampled too when one slice exceeds DUMP_BYTES); DIR/iterations_done.npy: the iterations run per slice (float64)."""
+    n, nil, nxl = out.shape
+    rng = np.random.default_rng(20251016)
+    row_bytes = nxl * out.dtype.itemsize
+    rows = np.arange(nil)
+    if nil * row_bytes > DUMP_BYTES:
+        rows = np.sort(rng.choice(nil, size=DUMP_BYTES // row_bytes, replace=False))
+    k = max(1, min(n, DUMP_BYTES // (len(rows) * row_bytes)))
+    pick = np.sort(rng.choice(n, size=k, replace=False))
+    res = np.stack([out.download(int(s), 1)[0][rows] for s in pick])
+    if np.iscomplexobj(res):
+        res = res.view(res.real.dtype).reshape(res.shape + (2,))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "result.npy"), res)
+    np.save(os.path.join(dirname, "iterations_done.npy"), np.asarray(done, dtype=np.float64))
+
+
 class Ctx:
     """What every leg shares: this rank's device, device memory, fences -- and, for N > 1 only, torch and the process group."""
 
@@ -476,11 +516,11 @@ def run_leg(ctx, config, K_override, main, override=None):
     # ---- inputs, resident in HBM before the clock starts -----------------------------------------
     mask = (np.random.default_rng(42).random((nil, nxl)) >= missing).astype(np.uint8)   # shared trace mask
     mask_t = ctx.empty((nil, nxl), np.float32).upload(mask.astype(np.float32))
-    pool = noise_pool(nil, nxl)
+    pool = noise_pool(nil, nxl) if (density > 0 or args.full) else None   # (the random-spectrum cubes only)
     fft_plan = _ffi.Plan(nil, nxl, n_local, device=dev_index) if kind == "FFT" else None
     np_dtype = np.float32 if cfg["real"] else np.complex64
     x_obs = ctx.empty((n_local, nil, nxl), np_dtype)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and density == 0 and not override
+    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and density == 0 and not override   # (--full only)
     cpu_slices = None
     n_cpu = 0
     if want_cpu:   # the CPU baseline is a single-GPU-run extra (rank 0, N = 1)
@@ -562,15 +602,22 @@ def run_leg(ctx, config, K_override, main, override=None):
     first_s, (done, _, dev_ms) = timed(K)
     assert args.eps > 0 or (int(done.min()) == K and int(done.max()) == K)
     floor = 5 if main else 3
-    R = args.repeats if (args.repeats > 0 and main) else int(max(floor, min(15, math.ceil(1.5 / max(first_s, 1e-4)))))
-    if kind == "SHEARLET" and not (args.repeats > 0 and main):
+    if args.repeats > 0 and main:
+        R = args.repeats
+    elif not args.full:
+        R = 1   # a plain run times exactly K steps
+    elif kind == "SHEARLET":
         R = 3 if first_s < 4.0 else 2
+    else:
+        R = int(max(floor, min(15, math.ceil(1.5 / max(first_s, 1e-4)))))
     times, dev_times = [first_s], [dev_ms]
     for _ in range(R - 1):
-        sec, (_, _, dms) = timed(K)
+        sec, (done, _, dms) = timed(K)
         times.append(sec)
         dev_times.append(dms)
     seconds = float(np.median(times))
+    if main and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, done)
     # the timed job's result on the slices the CPU leg also computes (parity figure of the line; nothing below may overwrite it)
     gpu_first = out.download(0, n_cpu) if (cpu_slices is not None and kind != "SHEARLET" and args.eps == 0) else None
 
@@ -874,7 +921,7 @@ def run_leg(ctx, config, K_override, main, override=None):
 
     # ---- the trivial gather of the blocks (outside the timed steps): device tensors, one collective ----
     gather = None
-    if world > 1 and main:
+    if world > 1 and main and args.full:
         from pseudo_3d_interpolation_amd.sharding import gather_blocks, gather_blocks_to_root
         src = out.tensor.cpu() if ctx.rehearsal else out.tensor
         gather = {}
@@ -974,8 +1021,9 @@ def run_leg(ctx, config, K_override, main, override=None):
         "vs_baseline": None,
         "dtype": f"{dtype_s} (f32 arithmetic)",
         "data": ("synthetic: SURVEY 8d's generator for every slice (6 complex plane waves + 1% complex Gaussian noise from default_rng(1234 + s), random trace "
-                 "mask from default_rng(42)), generated on the host and uploaded before the clock starts; the first slices (those the cpu_baseline / parity leg "
-                 "computes) are the oracle's own arrays, the others its recipe and random stream re-stated in bench.py"
+                 "mask from default_rng(42)), generated on the host and uploaded before the clock starts; "
+                 + ("the first slices (those the cpu_baseline / parity leg computes) are the oracle's own arrays, the others its recipe and random stream "
+                    "re-stated in bench.py" if n_cpu else "its recipe and random stream re-stated in bench.py")
                  if density == 0 else
                  f"synthetic: {density} random spectral coefficients + 1% Gaussian noise per slice (seeded), random trace mask"),
         "config": {
@@ -1047,7 +1095,7 @@ def main():
     line = run_leg(ctx, args.config, args.steps, main=True)
     release(ctx)
     plain = all(v is None for v in (args.nil, args.nxl, args.nslices, args.missing, args.thresh_op)) and args.density == 0
-    if args.config == 2 and plain and not args.only_main:
+    if args.config == 2 and plain and args.full and not args.only_main:
         others = {}
         for c in ((1, 3, 4) if ctx.world == 1 else (4,)):
             t0 = time.perf_counter()

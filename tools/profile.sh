@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 cd /tmp
 # the default bench job without its side runs and with ONE timed repeat: the trace then holds the K-iteration schedule twice (timed
 # job + the profiled repeat), and every col_kernel / row_pipe64_kernel launch belongs to it
-BENCH="$REPO/bench.py --no-cpu-baseline --no-dense --repeats 1 --warmup 0 --steps ${PMC_NITER:-100} $@"
+BENCH="$REPO/bench.py --full --no-cpu-baseline --no-dense --repeats 1 --warmup 0 --steps ${PMC_NITER:-100} $@"
 echo "== kernel trace + stats"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $BENCH > $OUT/trace.log 2>&1 || { echo "trace run failed"; tail -5 $OUT/trace.log; exit 1; }
 grep "^{" $OUT/trace.log | tail -1 > $REPO/gpurun_out/profiles_$TAG/bench_line_under_trace.json

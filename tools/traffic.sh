@@ -9,7 +9,7 @@ OUT=$REPO/gpurun_out/traffic_c$CFG
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="$REPO/bench.py --config $CFG --only-main --no-cpu-baseline --no-dense --repeats 1 --warmup 0 --steps $STEPS"
+BENCH="$REPO/bench.py --full --config $CFG --only-main --no-cpu-baseline --no-dense --repeats 1 --warmup 0 --steps $STEPS"
 echo "== kernel trace + stats"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $BENCH > $OUT/trace.log 2>&1 || { echo "trace run failed"; tail -5 $OUT/trace.log; exit 1; }
 # (SQ_INSTS_VALU: vector instructions per dispatch -- the VALU-issue roofline of the kernels that are bound by it, tools/traffic.py)
