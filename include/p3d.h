@@ -344,6 +344,18 @@ int p3d_shearlet64_run(p3d_splan64* plan, const void* x, int dtype, const double
 int p3d_smooth_gaussian(int device, const float* x, size_t nslices, int ny, int nx, double sigma, double truncate, float* out);
 int p3d_smooth_median(int device, const float* x, size_t nslices, int ny, int nx, int size, float* out);
 
+/* ---- step-15 automatic gain control (functions/signal.py:325-409, zero padding) along the time axis ----------------------------
+ * x/out HOST float32 [nt][ntraces] (time-slow: the slice-major (twt, iline, xline) cube); win: samples (an even win is made odd);
+ * kind 0 = rms, 1 = mean, 2 = median; squared: sign(y) * y^2 of the gained trace; gain (may be NULL): HOST float32 [nt][ntraces],
+ * the gain function g (0 replaced by 1).  Cubes larger than the free device memory go through in chunks of traces. */
+int p3d_agc(int device, const float* x, size_t nt, size_t ntraces, int win, int kind, int squared, float* out, float* gain);
+
+/* ---- step-15 iline / xline upsampling (cube_postprocessing_3D.py:350-488) ---------------------------------------------------------
+ * x HOST [nslices][ny][nx], out HOST [nslices][my][mx], dtype P3D_F32 or P3D_C64.  Output line o of the iline axis reads source line
+ * iy[o] and, when wy[o] != 0, line iy[o] + 1 with weight wy[o] in [0, 1) (the same for the xline axis with ix / wx); float32 arithmetic. */
+int p3d_upsample(int device, const void* x, int dtype, size_t nslices, int ny, int nx, const int* iy, const float* wy, int my, const int* ix,
+                 const float* wx, int mx, void* out);
+
 #ifdef __cplusplus
 }
 #endif

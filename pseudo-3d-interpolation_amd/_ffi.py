@@ -97,6 +97,9 @@ PROTOTYPES = {
     "p3d_last_sparsity": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "p3d_smooth_gaussian": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "p3d_smooth_median": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_agc": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_upsample": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                               C.c_void_p, C.c_int, C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1117,6 +1120,42 @@ def smooth_slices(x, kind, device=0, **kw):
         check(lib().p3d_smooth_median(int(device), _ptr(x), n, ny, nx, int(kw["size"]), _ptr(out)))
     else:
         raise ValueError(f"unknown smoothing filter {kind!r}")
+    return out
+
+
+AGC_KIND = {"rms": 0, "mean": 1, "median": 2}
+
+
+def agc(x, win, kind="rms", squared=False, return_gain=False, device=0):
+    """Automatic gain control along axis 0 of a float32 array [nt][ntraces...] (include/p3d.h, p3d_agc); returns a new array
+    (and the gain function when ``return_gain``)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim < 1 or x.size == 0:
+        raise ValueError("expected a non-empty array with time on axis 0")
+    nt = x.shape[0]
+    ntr = x.size // nt
+    out = np.empty_like(x)
+    gain = np.empty_like(x) if return_gain else None
+    check(lib().p3d_agc(int(device), _ptr(x), nt, ntr, int(win), AGC_KIND[kind], int(bool(squared)), _ptr(out),
+                        None if gain is None else _ptr(gain)))
+    return (out, gain) if return_gain else out
+
+
+def upsample_slices(x, iy, wy, ix, wx, device=0):
+    """Separable linear / nearest upsampling of a stack of (ny, nx) slices, float32 or complex64 (include/p3d.h, p3d_upsample):
+    output line o of an axis reads source line idx[o] and, with weight w[o], line idx[o] + 1."""
+    x = np.asarray(x)
+    if x.ndim != 3:
+        raise ValueError("expected a stack of slices (n, ny, nx)")
+    if np.iscomplexobj(x):
+        x, dtype = np.ascontiguousarray(x, dtype=np.complex64), P3D_C64
+    else:
+        x, dtype = np.ascontiguousarray(x, dtype=np.float32), P3D_F32
+    iy, ix = np.ascontiguousarray(iy, dtype=np.int32), np.ascontiguousarray(ix, dtype=np.int32)
+    wy, wx = np.ascontiguousarray(wy, dtype=np.float32), np.ascontiguousarray(wx, dtype=np.float32)
+    n, ny, nx = x.shape
+    out = np.empty((n, iy.size, ix.size), x.dtype)
+    check(lib().p3d_upsample(int(device), _ptr(x), dtype, n, ny, nx, _ptr(iy), _ptr(wy), iy.size, _ptr(ix), _ptr(wx), ix.size, _ptr(out)))
     return out
 
 

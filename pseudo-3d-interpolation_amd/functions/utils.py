@@ -1,4 +1,4 @@
-"""Small utilities mirrored from pseudo_3D_interpolation/functions/utils.py (only what steps 12-14 use)."""
+"""Small utilities mirrored from pseudo_3D_interpolation/functions/utils.py (only what steps 12-15 use)."""
 import numpy as np
 
 
@@ -35,3 +35,15 @@ def rescale_dask(a, vmin=0, vmax=1, amin=None, amax=None):
     if amin == amax:
         return a
     return vmin + (a - amin) * ((vmax - vmin) / (amax - amin))
+
+
+def convert_twt(twt, unit_in: str, unit_out: str):
+    """Convert TWT value(s) between 's', 'ms', 'us' and 'ns' (functions/utils.py:366-400, with its conversion factor)."""
+    units = {'s': 1, 'ms': 1e-3, 'us': 1e-6, 'ns': 1e-9}
+    if unit_in not in units:
+        raise ValueError(f'Input unit `{unit_in}` is not supported. Choose one of {units.keys()}')
+    if unit_out not in units:
+        raise ValueError(f'Output unit `{unit_out}` is not supported. Choose one of {units.keys()}')
+    fact_in, fact_out = units[unit_in], units[unit_out]
+    factor = fact_in / fact_out if fact_in > fact_out else fact_in * fact_out
+    return twt * factor
