@@ -350,6 +350,55 @@ int p3d_smooth_median(int device, const float* x, size_t nslices, int ny, int nx
  * the gain function g (0 replaced by 1).  Cubes larger than the free device memory go through in chunks of traces. */
 int p3d_agc(int device, const float* x, size_t nt, size_t ntraces, int win, int kind, int squared, float* out, float* gain);
 
+/* the same on DEVICE buffers [nt][ntraces] (x_dev != out_dev; gain_dev may be NULL), one pass over the whole cube (no chunking) */
+int p3d_agc_dev(int device, const float* x_dev, size_t nt, size_t ntraces, int win, int kind, int squared, float* out_dev, float* gain_dev);
+
+/* ---- step-11 pre-processing (cube_preprocessing_3D.py), csrc/p3d_preproc.hip ------------------------------------------------------
+ * Every cube argument is a DEVICE float32 matrix [nt][ntraces] (time-slow); every table argument is a HOST array designed in NumPy.
+ * Callers split cubes larger than the device memory into chunks of traces (every operation is per trace).
+ *   p3d_pre_reduce_dev:  res[ntraces] = rms (kind 0, sqrt(sum x^2 / nt)) or max |x| (kind 1) of every trace, 0 replaced by 1;
+ *       kind 2: the rms without that replacement.
+ *   p3d_pre_balance_dev: the same into ref[ntraces], then out = x / ref (trace balancing).
+ *   p3d_pre_gain_dev:    the reference's gain() along twt.  prm: doubles indexed by P3D_GAIN_* (flags: OR of the P3D_GAIN_* bits);
+ *       curves: HOST [4][nt] doubles (tpow, epow, linear, pgc factors; pgc is applied in float32), NULL when no curve is used; work:
+ *       DEVICE [nt][ntraces] floats, needed with AGC, qclip or norm_rms splitting the pass (may be NULL otherwise).
+ *   p3d_pre_sosfiltfilt_dev: scipy.signal.sosfiltfilt(sos, x, padtype='odd', padlen) along twt, sos / zi HOST [nsec][6] / [nsec][2]
+ *       (sosfilt_zi), double-precision recursion; work: DEVICE [nt + 2 padlen][ntraces] floats or NULL (allocated).
+ *   p3d_pre_upfirdn_dev: out[i] = sum_q h[(pre_remove + i) down - up q] x[q], i < nout (scipy's resample_poly after its padding).
+ *   p3d_pre_spectral_dev: forward FFT of x at length nt; Z[k] = op(fac[k] X[src[k] >> 2]) for k < num (op = src & 3: 0 plain, 1
+ *       conjugate, 2 real part; src < 0: 0); inverse FFT at length num (unnormalised); out = |Z| * s1 (modulus) or Re Z * s1 * s2.
+ *       FFT lengths up to 10240 (P3D_ERR_UNSUPPORTED beyond); work: DEVICE (nt + num) * ntraces complex64 or NULL (allocated). */
+enum {
+    P3D_GAIN_FLAGS = 0, P3D_GAIN_BIAS = 1, P3D_GAIN_GPOW = 2, P3D_GAIN_AGC_WIN = 3, P3D_GAIN_AGC_KIND = 4, P3D_GAIN_AGC_SQRT = 5,
+    P3D_GAIN_CLIP = 6, P3D_GAIN_PCLIP = 7, P3D_GAIN_NCLIP = 8, P3D_GAIN_QCLIP = 9, P3D_GAIN_SCALE = 10, P3D_GAIN_NPRM = 11
+};
+/* flag bits (prm[P3D_GAIN_FLAGS]); the bit of an entry with a parameter has the entry's name with an F_ prefix */
+#define P3D_GAIN_F_BIAS 1u
+#define P3D_GAIN_F_TPOW 2u
+#define P3D_GAIN_F_EPOW 4u
+#define P3D_GAIN_F_GPOW 8u
+#define P3D_GAIN_F_AGC 16u
+#define P3D_GAIN_F_CLIP 32u
+#define P3D_GAIN_F_PCLIP 64u
+#define P3D_GAIN_F_NCLIP 128u
+#define P3D_GAIN_F_QCLIP 256u
+#define P3D_GAIN_F_LINEAR 512u
+#define P3D_GAIN_F_PGC 1024u
+#define P3D_GAIN_F_NORM_RMS 2048u
+#define P3D_GAIN_F_SCALE 4096u
+#define P3D_GAIN_F_NORM 8192u
+#define P3D_GAIN_NBITS 14
+int p3d_pre_reduce_dev(int device, const float* x_dev, size_t nt, size_t ntraces, int kind, float* res_dev);
+int p3d_pre_balance_dev(int device, const float* x_dev, size_t nt, size_t ntraces, int kind, float* out_dev, float* ref_dev);
+int p3d_pre_gain_dev(int device, const float* x_dev, size_t nt, size_t ntraces, const double* prm, const double* curves, float* out_dev,
+                     float* work_dev);
+int p3d_pre_sosfiltfilt_dev(int device, const float* x_dev, size_t nt, size_t ntraces, int nsec, const double* sos, const double* zi, int padlen,
+                            float* out_dev, float* work_dev);
+int p3d_pre_upfirdn_dev(int device, const float* x_dev, size_t nt, size_t ntraces, const double* h, int nh, int up, int down, long long pre_remove,
+                        size_t nout, float* out_dev);
+int p3d_pre_spectral_dev(int device, const float* x_dev, size_t nt, size_t ntraces, int num, const int* src, const float* fac, int modulus,
+                         double s1, double s2, float* out_dev, void* work_dev);
+
 /* ---- step-15 iline / xline upsampling (cube_postprocessing_3D.py:350-488) ---------------------------------------------------------
  * x HOST [nslices][ny][nx], out HOST [nslices][my][mx], dtype P3D_F32 or P3D_C64.  Output line o of the iline axis reads source line
  * iy[o] and, when wy[o] != 0, line iy[o] + 1 with weight wy[o] in [0, 1) (the same for the xline axis with ix / wx); float32 arithmetic. */

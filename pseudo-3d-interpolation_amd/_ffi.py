@@ -98,6 +98,16 @@ PROTOTYPES = {
     "p3d_smooth_gaussian": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p]),
     "p3d_smooth_median": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "p3d_agc": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_agc_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_pre_reduce_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p]),
+    "p3d_pre_balance_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_pre_gain_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3d_pre_sosfiltfilt_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p]),
+    "p3d_pre_upfirdn_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                      C.c_size_t, C.c_void_p]),
+    "p3d_pre_spectral_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                       C.c_double, C.c_void_p, C.c_void_p]),
     "p3d_upsample": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                C.c_void_p, C.c_int, C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
@@ -1196,3 +1206,120 @@ def multi_run(x, mask, tau, niter, devices, thresh_op="hard", version="regular",
     check(lib().p3d_multi_run(len(dev), _ptr(dev), nil, nxl, _ptr(xc), dt, _ptr(m), _ptr(t), None if act is None else _ptr(act),
                               C.byref(prm), _ptr(out), n, _ptr(done), _ptr(sums)))
     return out, done, sums
+
+
+# ---- step 11: trace-wise pre-processing on device buffers (include/p3d.h, p3d_pre_*_dev) ----------------------------------------------
+GAIN_FLAG = {"bias": 1, "tpow": 2, "epow": 4, "gpow": 8, "agc": 16, "clip": 32, "pclip": 64, "nclip": 128, "qclip": 256, "linear": 512,
+             "pgc": 1024, "norm_rms": 2048, "scale": 4096, "norm": 8192}
+GAIN_PRM = {"flags": 0, "bias": 1, "gpow": 2, "agc_win": 3, "agc_kind": 4, "agc_sqrt": 5, "clip": 6, "pclip": 7, "nclip": 8, "qclip": 9,
+            "scale": 10}
+GAIN_NPRM = 11
+PRE_CHUNK_TRACES = None     # traces per device chunk of trace_ops (None: as many as half of the free device memory holds)
+
+
+def _op_len(op, nt):
+    """Trace length after one operation of :func:`trace_ops`."""
+    kind = op[0]
+    if kind == "upfirdn":
+        return int(op[5])
+    if kind == "spectral":
+        return int(op[1])
+    return nt
+
+
+def _run_op(op, device, src, dst, work, nt, ntr, extras):
+    kind = op[0]
+    if kind == "reduce":
+        ref = DeviceArray((ntr,), np.float32, device)
+        check(lib().p3d_pre_reduce_dev(device, src, nt, ntr, int(op[1]), ref.ptr))
+        check(lib().p3d_dev_memcpy(device, dst, src, 4 * nt * ntr, 2))
+        extras.append(ref)
+    elif kind == "balance":
+        ref = DeviceArray((ntr,), np.float32, device)
+        check(lib().p3d_pre_balance_dev(device, src, nt, ntr, int(op[1]), dst, ref.ptr))
+        extras.append(ref)
+    elif kind == "gain":
+        prm = np.ascontiguousarray(op[1], dtype=np.float64)
+        curves = None if op[2] is None else np.ascontiguousarray(op[2], dtype=np.float64)
+        check(lib().p3d_pre_gain_dev(device, src, nt, ntr, _ptr(prm), None if curves is None else _ptr(curves), dst, work))
+    elif kind == "agc":
+        check(lib().p3d_agc_dev(device, src, nt, ntr, int(op[1]), AGC_KIND[op[2]], int(bool(op[3])), dst, None))
+    elif kind == "filter":
+        sos = np.ascontiguousarray(op[1], dtype=np.float64)
+        zi = np.ascontiguousarray(op[2], dtype=np.float64)
+        check(lib().p3d_pre_sosfiltfilt_dev(device, src, nt, ntr, sos.shape[0], _ptr(sos), _ptr(zi), int(op[3]), dst, work))
+    elif kind == "upfirdn":
+        h = np.ascontiguousarray(op[1], dtype=np.float64)
+        check(lib().p3d_pre_upfirdn_dev(device, src, nt, ntr, _ptr(h), h.size, int(op[2]), int(op[3]), int(op[4]), int(op[5]), dst))
+    elif kind == "spectral":
+        srci = np.ascontiguousarray(op[2], dtype=np.int32)
+        fac = np.ascontiguousarray(op[3], dtype=np.float32)
+        check(lib().p3d_pre_spectral_dev(device, src, nt, ntr, int(op[1]), _ptr(srci), _ptr(fac), int(bool(op[4])), float(op[5]), float(op[6]),
+                                         dst, work))
+    else:
+        raise ValueError(f"unknown trace operation {kind!r}")
+
+
+def trace_ops(x, ops, device=0, chunk_traces=None):
+    """Run a chain of step-11 operations along axis 0 of a float32 array [nt][traces...] on the GPU.
+
+    The traces go to the device in chunks (``chunk_traces``, else ``PRE_CHUNK_TRACES``, else as many as half of the free device memory
+    holds); every operation of the chain runs on the chunk's device buffers, and the chunk comes back once.  ``ops`` are tuples:
+    ``('balance', kind)`` (0 rms, 1 max; its reference amplitudes are returned), ``('reduce', kind)`` (the same amplitudes, data
+    unchanged; kind 2: the rms without the 0 -> 1 guard), ``('gain', prm, curves)``, ``('agc', win, kind,
+    squared)``, ``('filter', sos, zi, padlen)``, ``('upfirdn', h, up, down, pre_remove, nout)``, ``('spectral', num, src, fac, modulus,
+    s1, s2)`` (include/p3d.h).  Returns ``(y, refs)``: y float32 [nt_out][traces...], refs one float32 array [traces...] per balance."""
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim < 1 or x.size == 0:
+        raise ValueError("expected a non-empty array with time on axis 0")
+    nt = x.shape[0]
+    tshape = x.shape[1:]
+    ntr = x.size // nt
+    x2 = x.reshape(nt, ntr)
+    lens = [nt]
+    for op in ops:
+        lens.append(_op_len(op, lens[-1]))
+    ntmax = max(lens)
+    pad = max([int(op[3]) for op in ops if op[0] == "filter"] or [0])
+    # per trace: two float buffers, the work buffer (float / filter extension / two complex64 lines)
+    work_per_trace = max(4 * ntmax, 4 * (ntmax + 2 * pad), 8 * 2 * ntmax)
+    per_trace = 2 * 4 * ntmax + work_per_trace
+    chunk = chunk_traces or PRE_CHUNK_TRACES
+    if not chunk:
+        free, _ = device_mem_info(device)
+        chunk = max(1, (free // 2) // per_trace)
+    chunk = int(min(chunk, ntr, 2 ** 31 - 1))   # the entry points take at most 2^31 - 1 traces per call
+    y = np.empty((lens[-1], ntr), np.float32)
+    nbal = sum(1 for op in ops if op[0] in ("balance", "reduce"))
+    refs = [np.empty(ntr, np.float32) for _ in range(nbal)]
+    bufs = [DeviceArray((ntmax * chunk,), np.float32, device) for _ in range(2)]
+    work = DeviceArray((work_per_trace * chunk // 4,), np.float32, device)
+    try:
+        for j0 in range(0, ntr, chunk):
+            n = min(chunk, ntr - j0)
+            piece = np.ascontiguousarray(x2[:, j0:j0 + n])
+            check(lib().p3d_dev_memcpy(device, bufs[0].ptr, _ptr(piece), piece.nbytes, 0))
+            cur, extras = 0, []
+            for op, ln in zip(ops, lens[:-1]):
+                _run_op(op, device, bufs[cur].ptr, bufs[1 - cur].ptr, work.ptr, ln, n, extras)
+                cur = 1 - cur
+            out = np.empty((lens[-1], n), np.float32)
+            check(lib().p3d_dev_memcpy(device, _ptr(out), bufs[cur].ptr, out.nbytes, 1))
+            y[:, j0:j0 + n] = out
+            for r, e in zip(refs, extras):
+                r[j0:j0 + n] = e.download()
+                e.free()
+    finally:
+        for b in bufs + [work]:
+            b.free()
+    return y.reshape((lens[-1],) + tshape), [r.reshape(tshape) for r in refs]
+
+
+def apply_trace_op(x, axis, op, device=0):
+    """One operation of :func:`trace_ops` along ``axis`` of ``x`` (moved to the front on the host and back); float32 result."""
+    x = np.asarray(x, dtype=np.float32)
+    axis = axis % x.ndim
+    xt = np.moveaxis(x, axis, 0) if axis != 0 else x
+    y, refs = trace_ops(xt, [op], device=device)
+    y = np.moveaxis(y, 0, axis) if axis != 0 else y
+    return (y, refs) if op[0] in ("balance", "reduce") else y

@@ -226,4 +226,27 @@ int p3d_agc(int device, const float* x, size_t nt, size_t ntraces, int win, int 
     return P3D_OK;
 }
 
+int p3d_agc_dev(int device, const float* x, size_t nt, size_t ntraces, int win, int kind, int squared, float* out, float* gain)
+{
+    if (!x || !out) return afail(P3D_ERR_INVALID, "NULL buffer");
+    if (x == out) return afail(P3D_ERR_INVALID, "x and out must be different buffers");
+    if (nt < 1 || ntraces < 1) return afail(P3D_ERR_INVALID, "bad shape (nt %zu, ntraces %zu)", nt, ntraces);
+    if (win < 1) return afail(P3D_ERR_INVALID, "window of %d samples", win);
+    if (kind != AGC_RMS && kind != AGC_MEAN && kind != AGC_MEDIAN) return afail(P3D_ERR_INVALID, "unknown AGC kind %d", kind);
+    if (win % 2 == 0) ++win;
+    const int h = win / 2;
+    int ndev = 0;
+    A_TRY(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return afail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
+    A_TRY(hipSetDevice(device));
+    const unsigned blocks = (unsigned)((ntraces + 255) / 256);
+    if (kind == AGC_MEDIAN)
+        agc_median_kernel<<<blocks, 256>>>(x, out, gain, (long long)nt, (long long)ntraces, h, squared);
+    else
+        agc_sum_kernel<<<blocks, 256>>>(x, out, gain, (long long)nt, (long long)ntraces, h, win, kind, squared);
+    A_TRY(hipGetLastError());
+    A_TRY(hipDeviceSynchronize());
+    return P3D_OK;
+}
+
 }  // extern "C"

@@ -1789,7 +1789,7 @@ static double fft_freq(int k, int nfft, double dt) { return (k < (nfft + 1) / 2 
 
 // One transform along axis 0 of a row-major [nfft][ntr] complex matrix on the device, in place.  Lengths with tuned or flexible
 // column kernels run those (eight traces per workgroup, 64-byte pieces); longer ones the line-per-workgroup fallback.
-static int axis0_fft(int device, c32* work, int nfft, size_t ntr, int inverse)
+static int axis0_fft_impl(int device, c32* work, int nfft, size_t ntr, int inverse)
 {
     // (the column kernels address a row-major matrix with 32-bit element offsets)
     const LineOps* ops = (double)nfft * (double)ntr < 4294967296.0 ? find_ops(nfft) : nullptr;
@@ -1849,7 +1849,7 @@ int p3d_time2freq_dev(int device, const float* x, int nt, size_t ntr, double dt,
     HIP_TRY(hipMemcpy(dfac.p, fac.data(), sizeof(c32) * nfreq, hipMemcpyHostToDevice));
     c32* work = (c32*)dwork.p;
     HIP_TRY(gen_launch_t2f_pad(x, work, nt, nfft, ntr, nullptr));
-    if ((rc = axis0_fft(device, work, nfft, ntr, 0))) return rc;
+    if ((rc = axis0_fft_impl(device, work, nfft, ntr, 0))) return rc;
     HIP_TRY(gen_launch_scale_rows(work, (c32*)out, (const c32*)dfac.p, nfreq, ntr, nullptr));
     HIP_TRY(hipDeviceSynchronize());
     return P3D_OK;
@@ -1902,7 +1902,7 @@ int p3d_freq2time_dev(int device, const void* X, int nfreq, const int32_t* kidx,
     HIP_TRY(hipMemcpy(dsrc.p, src.data(), sizeof(int) * nfft, hipMemcpyHostToDevice));
     c32* work = (c32*)dwork.p;
     HIP_TRY(gen_launch_f2t_fill((const c32*)X, work, (const c32*)dfac.p, (const int*)dsrc.p, nfft, ntr, nullptr));
-    if ((rc = axis0_fft(device, work, nfft, ntr, 1))) return rc;
+    if ((rc = axis0_fft_impl(device, work, nfft, ntr, 1))) return rc;
     // true_amplitude: the inverse carries 1/(nfft*dt)
     HIP_TRY(gen_launch_real_part(work, out, (size_t)nfft * ntr, (float)(1.0 / (nfft * dt)), nullptr));
     HIP_TRY(hipDeviceSynchronize());
@@ -1943,6 +1943,12 @@ int p3d_last_profile(p3d_plan* p, double* col_ms, int* col_n, double* row_ms, in
 }
 
 }  // extern "C"
+
+// the line FFT of steps 12 / 14 for the step-11 unit (p3d_internal.hpp)
+namespace p3d {
+int axis0_fft(int device, c32* work, int nfft, size_t ntr, int inverse) { return axis0_fft_impl(device, work, nfft, ntr, inverse); }
+bool axis0_fft_supported(int nfft) { return nfft >= 1 && nfft <= GEN_MAX_N && gen_make_plan(nfft).nf >= 0; }
+}  // namespace p3d
 
 
 // ---- several devices from one process ----------------------------------------------------------------------------------------

@@ -7,6 +7,12 @@
 
 namespace p3d {
 
+// One in-place transform along axis 0 of a row-major [nfft][ntr] complex64 matrix on the device (unnormalised, numpy.fft sign
+// conventions; p3d_api.hip), the any-length line FFT of steps 12 and 14, also used by step 11 (p3d_preproc.hip).  Synchronises the device.
+int axis0_fft(int device, c32* work, int nfft, size_t ntr, int inverse);
+bool axis0_fft_supported(int nfft);   // 1 <= nfft <= GEN_MAX_N with a plan
+
+
 // A threshold of the host's float64 schedule as the float32 kernels get it.  The reference compares FLOAT32 moduli with a FLOAT64
 // (complex128) threshold in double precision -- np.less(np.absolute(X), tau) with tau a NumPy float64 / complex128 scalar
 // (threshold_operator.py:110-112; NEP 50 promotes the comparison, complex operands compare lexicographically).  For a float v and a

@@ -1,5 +1,10 @@
-"""Small utilities mirrored from pseudo_3D_interpolation/functions/utils.py (only what steps 12-15 use)."""
+"""Small utilities mirrored from pseudo_3D_interpolation/functions/utils.py (only what steps 11-15 use)."""
+from functools import partial
+
 import numpy as np
+
+# shortest positional representation of a float (trailing zeros and point trimmed)
+ffloat = partial(np.format_float_positional, trim='-')
 
 
 def xprint(*args, kind: str = 'info', verbosity: int = 0, **kwargs) -> None:
