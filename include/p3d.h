@@ -405,6 +405,21 @@ int p3d_pre_spectral_dev(int device, const float* x_dev, size_t nt, size_t ntrac
 int p3d_upsample(int device, const void* x, int dtype, size_t nslices, int ny, int nx, const int* iy, const float* wy, int my, const int* ix,
                  const float* wx, int mx, void* out);
 
+/* ---- step-10 trace stacking into the binned cube (cube_binning_3D.py:922-1240), csrc/p3d_binning.hip -----------------------------------
+ * CSR input built by the host: traces sorted into bin order, bin b = il * nxl + xl owns traces bin_start[b] .. bin_start[b + 1] - 1
+ * (bin_start: nil * nxl + 1 entries over ALL bins, from 0 to ntraces).  Trace t: samples[trace_off[t] .. + trace_len[t]) (float32);
+ * its sample i lands on output sample j = i + shift[t], zero outside 0 <= i < trace_len[t] (the padding counts).  weight: normalised
+ * float64 weights (IDW only, may be NULL otherwise).  out: [nt][nil][nxl] float32 (slice-major), empty bins 0.
+ * method 0 = average (double sum / k), 1 = median (exact, np.median of the float32 stack), 2 = nearest (the first trace of the bin),
+ * 3 = IDW (double sum of w * x).  No atomics: bitwise repeatable.
+ *   p3d_bin_stack: HOST buffers; runs in chunks of whole inlines so that the chunk's cube slab, its span of samples and its tables fit in
+ *       half of the free device memory, or in max_bytes when that is smaller (0: no cap); a single inline beyond it is P3D_ERR_UNSUPPORTED.
+ *   p3d_bin_stack_dev: DEVICE buffers, one launch over the whole cube. */
+int p3d_bin_stack(int device, const float* samples, const long long* trace_off, const int* trace_len, const int* shift, const double* weight,
+                  size_t ntraces, const long long* bin_start, int nil, int nxl, int nt, int method, size_t max_bytes, float* out);
+int p3d_bin_stack_dev(int device, const float* samples_dev, const long long* trace_off_dev, const int* trace_len_dev, const int* shift_dev,
+                      const double* weight_dev, const long long* bin_start_dev, int nil, int nxl, int nt, int method, float* out_dev);
+
 #ifdef __cplusplus
 }
 #endif

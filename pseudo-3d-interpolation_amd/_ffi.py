@@ -110,6 +110,10 @@ PROTOTYPES = {
                                        C.c_double, C.c_void_p, C.c_void_p]),
     "p3d_upsample": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                C.c_void_p, C.c_int, C.c_void_p]),
+    "p3d_bin_stack": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p]),
+    "p3d_bin_stack_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1167,6 +1171,53 @@ def upsample_slices(x, iy, wy, ix, wx, device=0):
     out = np.empty((n, iy.size, ix.size), x.dtype)
     check(lib().p3d_upsample(int(device), _ptr(x), dtype, n, ny, nx, _ptr(iy), _ptr(wy), iy.size, _ptr(ix), _ptr(wx), ix.size, _ptr(out)))
     return out
+
+
+BIN_METHOD = {"average": 0, "median": 1, "nearest": 2, "IDW": 3}
+
+
+def _bin_tables(samples, trace_off, trace_len, shift, weight, bin_start, nil, nxl, method):
+    samples = np.ascontiguousarray(samples, dtype=np.float32).ravel()
+    trace_off = np.ascontiguousarray(trace_off, dtype=np.int64)
+    trace_len = np.ascontiguousarray(trace_len, dtype=np.int32)
+    shift = np.ascontiguousarray(shift, dtype=np.int32)
+    bin_start = np.ascontiguousarray(bin_start, dtype=np.int64)
+    ntr = trace_off.size
+    if trace_len.size != ntr or shift.size != ntr or bin_start.size != int(nil) * int(nxl) + 1:
+        raise ValueError("inconsistent binning tables")
+    if ntr and int((trace_off + trace_len).max()) > samples.size:
+        raise ValueError("a trace reaches past the end of the sample buffer")
+    if method not in BIN_METHOD:
+        raise ValueError(f"unknown stacking method {method!r} (use one of {sorted(BIN_METHOD)})")
+    if method == "IDW":
+        if weight is None:
+            raise ValueError("IDW needs weights")
+        weight = np.ascontiguousarray(weight, dtype=np.float64)
+        if weight.size != ntr:
+            raise ValueError("one weight per trace")
+    else:
+        weight = None
+    return samples, trace_off, trace_len, shift, weight, bin_start
+
+
+def bin_stack(samples, trace_off, trace_len, shift, bin_start, nil, nxl, nt, method="average", weight=None, max_bytes=0, device=0):
+    """Stack the traces of every (iline, xline) bin into a slice-major float32 cube [nt][nil][nxl] (include/p3d.h, p3d_bin_stack).
+    CSR layout: traces in bin order, bin ``il * nxl + xl`` owns traces ``bin_start[b] .. bin_start[b + 1]``; trace t's sample i lands on
+    output sample ``i + shift[t]``.  ``max_bytes`` caps the device memory of one chunk of inlines (0: half of the free memory)."""
+    samples, trace_off, trace_len, shift, weight, bin_start = _bin_tables(samples, trace_off, trace_len, shift, weight, bin_start, nil, nxl,
+                                                                         method)
+    out = np.empty((int(nt), int(nil), int(nxl)), np.float32)
+    check(lib().p3d_bin_stack(int(device), _ptr(samples), _ptr(trace_off), _ptr(trace_len), _ptr(shift), None if weight is None else _ptr(weight),
+                              trace_off.size, _ptr(bin_start), int(nil), int(nxl), int(nt), BIN_METHOD[method], int(max_bytes), _ptr(out)))
+    return out
+
+
+def bin_stack_dev(samples, trace_off, trace_len, shift, bin_start, out, nil, nxl, nt, method="average", weight=None, device=0):
+    """p3d_bin_stack_dev on device pointers (integers, e.g. from `DeviceBuffer.ptr`); ``out`` receives [nt][nil][nxl] float32."""
+    if method not in BIN_METHOD:
+        raise ValueError(f"unknown stacking method {method!r}")
+    check(lib().p3d_bin_stack_dev(int(device), samples, trace_off, trace_len, shift, weight, bin_start, int(nil), int(nxl), int(nt),
+                                  BIN_METHOD[method], out))
 
 
 def _host_cube(x):

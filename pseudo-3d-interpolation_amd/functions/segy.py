@@ -1,0 +1,179 @@
+"""Minimal SEG-Y reader and writer (NumPy only).
+
+Layout: a 3200-byte textual header (EBCDIC or ASCII), a 400-byte binary header, ``n`` 3200-byte extended textual headers (binary
+header bytes 3505-3506), then fixed-length traces of a 240-byte header and ``ns`` samples, all big-endian.  Sample formats 1 (IBM
+float), 2 (int32), 3 (int16), 5 (IEEE float) and 8 (int8).  The file is memory-mapped as one structured array per trace, so headers
+and samples are read without copying the file; samples are converted to float32 on access.
+
+Trace header fields (1-based byte positions, the ones step 10 scrapes): 1 TRACE_SEQUENCE_LINE, 5 TRACE_SEQUENCE_FILE, 9 FieldRecord,
+71 SourceGroupScalar, 73 SourceX, 77 SourceY, 109 DelayRecordingTime, 115 TRACE_SAMPLE_COUNT, 117 TRACE_SAMPLE_INTERVAL (microseconds)."""
+import numpy as np
+
+TEXT_BYTES, BIN_BYTES, TRACE_HEADER_BYTES = 3200, 400, 240
+
+# name: (1-based byte, big-endian dtype)
+TRACE_FIELDS = {
+    'TRACE_SEQUENCE_LINE': (1, '>i4'),
+    'TRACE_SEQUENCE_FILE': (5, '>i4'),
+    'FieldRecord': (9, '>i4'),
+    'SourceGroupScalar': (71, '>i2'),
+    'SourceX': (73, '>i4'),
+    'SourceY': (77, '>i4'),
+    'DelayRecordingTime': (109, '>i2'),
+    'TRACE_SAMPLE_COUNT': (115, '>u2'),
+    'TRACE_SAMPLE_INTERVAL': (117, '>u2'),
+}
+# binary header: name: (1-based byte in the file, dtype)
+BIN_FIELDS = {
+    'Interval': (3217, '>u2'),
+    'Samples': (3221, '>u2'),
+    'Format': (3225, '>i2'),
+    'SEGYRevision': (3501, '>u2'),
+    'TraceFlag': (3503, '>i2'),
+    'ExtendedHeaders': (3505, '>i2'),
+}
+SAMPLE_DTYPE = {1: '>u4', 2: '>i4', 3: '>i2', 5: '>f4', 8: 'i1'}
+
+
+def ibm2ieee(words):
+    """IBM System/360 single-precision words (uint32) -> float32: (-1)^s * 0.m (24 bits) * 16^(e - 64)."""
+    u = np.asarray(words, dtype=np.uint32)
+    sign = np.where(u >> 31, -1.0, 1.0)
+    expo = ((u >> 24) & 0x7F).astype(np.int64)
+    mant = (u & 0x00FFFFFF).astype(np.float64)
+    return (sign * np.ldexp(mant, 4 * (expo - 64) - 24)).astype(np.float32)
+
+
+def ieee2ibm(values):
+    """float32 -> IBM words (uint32), mantissa rounded to nearest; |x| beyond the IBM range saturates, below it flushes to 0."""
+    x = np.asarray(values, dtype=np.float64)
+    a = np.abs(x)
+    out = np.zeros(x.shape, np.uint32)
+    nz = a > 0
+    e = np.zeros(x.shape, np.int64)
+    # a = m * 16^e with 1/16 <= m < 1
+    e[nz] = np.floor(np.log2(a[nz]) / 4).astype(np.int64) + 1
+    m = np.zeros(x.shape)
+    m[nz] = np.ldexp(a[nz], -4 * e[nz])
+    lo = nz & (m < 1.0 / 16)                 # log2 rounding at the edges
+    e[lo] -= 1
+    m[lo] *= 16
+    hi = nz & (m >= 1.0)
+    e[hi] += 1
+    m[hi] /= 16
+    mant = np.rint(np.ldexp(m, 24)).astype(np.int64)
+    carry = mant >= (1 << 24)
+    mant[carry] >>= 4
+    e[carry] += 1
+    biased = e + 64
+    over = nz & (biased > 127)
+    under = nz & (biased < 0)
+    mant[over], biased[over] = 0xFFFFFF, 127
+    ok = nz & ~under
+    sign = (x < 0).astype(np.uint32) << 31
+    out[ok] = (sign[ok] | (biased[ok].astype(np.uint32) << 24) | mant[ok].astype(np.uint32))
+    return out
+
+
+def _trace_dtype(ns, fmt):
+    names, formats, offsets = [], [], []
+    for name, (byte, dt) in TRACE_FIELDS.items():
+        names.append(name)
+        formats.append(dt)
+        offsets.append(byte - 1)
+    names.append('data')
+    formats.append((SAMPLE_DTYPE[fmt], (ns,)))
+    offsets.append(TRACE_HEADER_BYTES)
+    return np.dtype({'names': names, 'formats': formats, 'offsets': offsets,
+                     'itemsize': TRACE_HEADER_BYTES + ns * np.dtype(SAMPLE_DTYPE[fmt]).itemsize})
+
+
+def _decode_text(raw):
+    if raw[:1] == b'C' or raw[:1].isascii() and raw[:1].isalnum():
+        return raw.decode('ascii', 'replace')
+    return raw.decode('cp500', 'replace')
+
+
+class SegyFile:
+    """A memory-mapped SEG-Y file: ``text`` (str), ``binary`` (dict), ``headers`` (structured array of the trace-header fields),
+    ``traces(rows)`` float32 samples [len(rows)][ns], ``dt`` (ms) and ``ns`` from the binary header."""
+
+    def __init__(self, path):
+        self.path = path
+        with open(path, 'rb') as f:
+            head = f.read(TEXT_BYTES + BIN_BYTES)
+        if len(head) < TEXT_BYTES + BIN_BYTES:
+            raise ValueError(f'{path}: shorter than the SEG-Y file headers')
+        self.text = _decode_text(head[:TEXT_BYTES])
+        self.binary = {k: int(np.frombuffer(head, dt, 1, b - 1)[0]) for k, (b, dt) in BIN_FIELDS.items()}
+        fmt = self.binary['Format']
+        if fmt not in SAMPLE_DTYPE:
+            raise NotImplementedError(f'{path}: sample format {fmt} (supported: {sorted(SAMPLE_DTYPE)})')
+        self.format, self.ns = fmt, self.binary['Samples']
+        self.dt = self.binary['Interval'] / 1000.0
+        start = TEXT_BYTES + BIN_BYTES + TEXT_BYTES * max(self.binary['ExtendedHeaders'], 0)
+        self._dtype = _trace_dtype(self.ns, fmt)
+        nbytes = np.memmap(path, np.uint8, 'r').size - start
+        if nbytes < 0 or nbytes % self._dtype.itemsize:
+            raise ValueError(f'{path}: {nbytes} trace bytes are not a whole number of {self._dtype.itemsize}-byte traces')
+        self.ntraces = nbytes // self._dtype.itemsize
+        self._mm = np.memmap(path, self._dtype, 'r', offset=start, shape=(self.ntraces,))
+
+    @property
+    def headers(self):
+        return self._mm[list(TRACE_FIELDS)]
+
+    def header(self, name):
+        return np.asarray(self._mm[name]).astype(np.int64)
+
+    def traces(self, rows=None):
+        raw = self._mm['data'] if rows is None else self._mm['data'][np.asarray(rows)]
+        if self.format == 1:
+            return ibm2ieee(raw)
+        return np.asarray(raw).astype(np.float32)
+
+
+def scaled_coordinates(scalar, x, y):
+    """The header scalar rule of the reference (cube_binning_3D.py:657-668): the sign of the FIRST trace's scalar decides for all;
+    negative: divide by |scalar|, otherwise multiply (a scalar of 0 gives 0, as there)."""
+    scalar = np.asarray(scalar, dtype=np.float64)
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if scalar.size and scalar[0] < 0:
+        return x / np.abs(scalar), y / np.abs(scalar)
+    return x * scalar, y * scalar
+
+
+def write_segy(path, data, dt_ms, fmt=5, headers=None, text=''):
+    """Write float samples ``data`` [ntraces][ns] as a SEG-Y file (revision 1, fixed-length traces).  ``headers``: optional dict of
+    trace-header field arrays (TRACE_FIELDS names); TRACE_SEQUENCE_LINE / _FILE default to 1 ... n, sample count and interval to the
+    file's."""
+    data = np.asarray(data, dtype=np.float32)
+    if data.ndim != 2:
+        raise ValueError('data is [ntraces][nsamples]')
+    ntr, ns = data.shape
+    dtype = _trace_dtype(ns, fmt)
+    rec = np.zeros(ntr, dtype)
+    rec['TRACE_SEQUENCE_LINE'] = np.arange(1, ntr + 1)
+    rec['TRACE_SEQUENCE_FILE'] = np.arange(1, ntr + 1)
+    rec['TRACE_SAMPLE_COUNT'] = ns
+    rec['TRACE_SAMPLE_INTERVAL'] = int(round(dt_ms * 1000))
+    for k, v in (headers or {}).items():
+        rec[k] = v
+    if fmt == 1:
+        rec['data'] = ieee2ibm(data)
+    elif fmt == 5:
+        rec['data'] = data
+    else:
+        info = np.iinfo(np.dtype(SAMPLE_DTYPE[fmt]))
+        rec['data'] = np.clip(np.rint(data), info.min, info.max)
+    txt = text.encode('cp500', 'replace')[:TEXT_BYTES].ljust(TEXT_BYTES, ' '.encode('cp500'))
+    binh = np.zeros(BIN_BYTES, np.uint8)
+    for k, v in {'Interval': int(round(dt_ms * 1000)), 'Samples': ns, 'Format': fmt, 'SEGYRevision': 0x0100, 'TraceFlag': 1,
+                 'ExtendedHeaders': 0}.items():
+        b, dt = BIN_FIELDS[k]
+        binh[b - 1 - TEXT_BYTES:b - 1 - TEXT_BYTES + np.dtype(dt).itemsize] = np.frombuffer(np.array(v, dt).tobytes(), np.uint8)
+    with open(path, 'wb') as f:
+        f.write(txt)
+        f.write(binh.tobytes())
+        f.write(rec.tobytes())
+    return path
