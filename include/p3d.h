@@ -420,6 +420,28 @@ int p3d_bin_stack(int device, const float* samples, const long long* trace_off, 
 int p3d_bin_stack_dev(int device, const float* samples_dev, const long long* trace_off_dev, const int* trace_len_dev, const int* shift_dev,
                       const double* weight_dev, const long long* bin_start_dev, int nil, int nxl, int nt, int method, float* out_dev);
 
+/* ---- step 8: despiking of a 2-D section (p3d_despike.hip; the reference's despike_2D) -------------------------------------------------------
+ * The section is trace-major [ntr][ns] float32, the layout of the SEG-Y file.  w: odd number of adjacent traces, 3 ... P3D_DESPIKE_MAX_TRACES
+ * (larger: P3D_ERR_UNSUPPORTED); mode 0 = mean, 1 = median, 2 = rms of |a| over the w traces of a window, per sample row.
+ *   detect: sample (t, x) is a candidate if |a[t][x]| > threshold * (the smallest window value among the windows that contain trace x), in
+ *       float32 with NumPy's order of summation.  Rows t < main_end (main view) or t >= add_start (additional view; pass INT_MAX for none) are
+ *       examined.  splits: nsplits + 1 ascending trace boundaries from 0 to ntr on the HOST (NULL / 0: one split); windows never cross one.
+ *       mask [ntr][(ns + 63) / 64]: bit t % 64 of word t / 64 of trace x; counts [2][ntr]: candidates per trace in the main / additional view.
+ *   replace: spike records of 8 ints (trace, lo, hi, first, last, c0, c1, 0) on the HOST, sorted by level; level l owns records
+ *       level_start[l] .. level_start[l + 1] and is one launch.  Rows lo .. hi of the trace are rewritten from columns c0 .. c1 (at most
+ *       P3D_DESPIKE_MAX_TRACES): out 0 = scaled (a / (max(a) / f(|win|)) * blackman, taper in double), 1 = mode (f(win)), 2 = threshold
+ *       (f(win) * threshold), 3 = zeros, 4 = median (np.median of win).
+ * The plain entry points take HOST sections / masks / counts, the _dev ones DEVICE buffers (the section never leaves the device between the two). */
+#define P3D_DESPIKE_MAX_TRACES 31
+int p3d_despike_detect(int device, const float* section, int ntr, int ns, int w, int mode, float threshold, int main_end, int add_start, const int* splits,
+                       int nsplits, unsigned long long* mask, int* counts);
+int p3d_despike_detect_dev(int device, const float* section_dev, int ntr, int ns, int w, int mode, float threshold, int main_end, int add_start,
+                           const int* splits, int nsplits, unsigned long long* mask_dev, int* counts_dev);
+int p3d_despike_replace(int device, float* section, int ntr, int ns, const int* spikes, size_t nspikes, const int* level_start, int nlevels, int mode, int out,
+                        float threshold);
+int p3d_despike_replace_dev(int device, float* section_dev, int ntr, int ns, const int* spikes, size_t nspikes, const int* level_start, int nlevels, int mode,
+                            int out, float threshold);
+
 #ifdef __cplusplus
 }
 #endif

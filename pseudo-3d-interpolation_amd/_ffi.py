@@ -114,6 +114,13 @@ PROTOTYPES = {
                                 C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p]),
     "p3d_bin_stack_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p]),
+    "p3d_despike_detect": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p]),
+    "p3d_despike_detect_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                         C.c_void_p, C.c_void_p]),
+    "p3d_despike_replace": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "p3d_despike_replace_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_float]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1218,6 +1225,85 @@ def bin_stack_dev(samples, trace_off, trace_len, shift, bin_start, out, nil, nxl
         raise ValueError(f"unknown stacking method {method!r}")
     check(lib().p3d_bin_stack_dev(int(device), samples, trace_off, trace_len, shift, weight, bin_start, int(nil), int(nxl), int(nt),
                                   BIN_METHOD[method], out))
+
+
+DESPIKE_MODE = {"mean": 0, "median": 1, "rms": 2}
+DESPIKE_OUT = {"scaled": 0, "mode": 1, "threshold": 2, "zeros": 3, "median": 4}
+DESPIKE_MAX_TRACES = 31      # P3D_DESPIKE_MAX_TRACES of include/p3d.h
+DESPIKE_NO_VIEW = 2**31 - 1  # add_start when there is no additional view
+
+
+def _despike_window(w, mode):
+    if mode not in DESPIKE_MODE:
+        raise ValueError(f"unknown amplitude mode {mode!r} (use one of {sorted(DESPIKE_MODE)})")
+    w = int(w)
+    if w % 2 == 0:
+        raise ValueError("Number of traces must be odd integer.")
+    if w > DESPIKE_MAX_TRACES:
+        raise UnsupportedError(P3D_ERR_UNSUPPORTED, f"trace windows of up to {DESPIKE_MAX_TRACES} traces are supported, got {w}")
+    return w
+
+
+def _despike_splits(splits, ntr):
+    if splits is None:
+        return None, 0
+    b = np.ascontiguousarray(splits, dtype=np.int32)
+    if b.ndim != 1 or b.size < 2 or b[0] != 0 or b[-1] != ntr or np.any(np.diff(b) <= 0):
+        raise ValueError("splits are ascending trace boundaries from 0 to the number of traces")
+    return b, b.size - 1
+
+
+def despike_detect(section, w, mode, threshold, main_end, add_start=None, splits=None, device=0):
+    """Candidate mask and per-view counts of a trace-major float32 section [ntr][ns] (include/p3d.h, p3d_despike_detect).  Returns
+    ``mask`` uint64 [ntr][ceil(ns / 64)] (bit t % 64 of word t // 64) and ``counts`` int32 [2][ntr] (main view, additional view)."""
+    w = _despike_window(w, mode)
+    section = np.ascontiguousarray(section, dtype=np.float32)
+    if section.ndim != 2:
+        raise ValueError("section is [ntraces][nsamples]")
+    ntr, ns = section.shape
+    b, nb = _despike_splits(splits, ntr)
+    mask = np.empty((ntr, (ns + 63) // 64), np.uint64)
+    counts = np.empty((2, ntr), np.int32)
+    check(lib().p3d_despike_detect(int(device), _ptr(section), ntr, ns, w, DESPIKE_MODE[mode], float(threshold), int(main_end),
+                                   DESPIKE_NO_VIEW if add_start is None else int(add_start), None if b is None else _ptr(b), nb, _ptr(mask), _ptr(counts)))
+    return mask, counts
+
+
+def despike_detect_dev(section, ntr, ns, w, mode, threshold, main_end, add_start, mask, counts, splits=None, device=0):
+    """p3d_despike_detect_dev on device pointers (``DeviceArray.ptr``): ``mask`` receives [ntr][ceil(ns / 64)] uint64, ``counts`` [2][ntr] int32."""
+    w = _despike_window(w, mode)
+    b, nb = _despike_splits(splits, ntr)
+    check(lib().p3d_despike_detect_dev(int(device), section, int(ntr), int(ns), w, DESPIKE_MODE[mode], float(threshold), int(main_end),
+                                       DESPIKE_NO_VIEW if add_start is None else int(add_start), None if b is None else _ptr(b), nb, mask, counts))
+
+
+def _despike_records(spikes, level_start, mode, out):
+    if mode not in DESPIKE_MODE:
+        raise ValueError(f"unknown amplitude mode {mode!r}")
+    if out not in DESPIKE_OUT:
+        raise ValueError(f"unknown output amplitude option {out!r}")
+    spikes = np.ascontiguousarray(spikes, dtype=np.int32).reshape(-1, 8)
+    level_start = np.ascontiguousarray(level_start, dtype=np.int32)
+    return spikes, level_start
+
+
+def despike_replace(section, spikes, level_start, mode, out, threshold, device=0):
+    """Replace the spikes of a trace-major float32 section [ntr][ns]; returns the new section.  ``spikes`` int32 [n][8] records
+    (trace, lo, hi, first, last, c0, c1, 0) sorted by level, ``level_start`` the offsets of the levels (include/p3d.h, p3d_despike_replace)."""
+    spikes, level_start = _despike_records(spikes, level_start, mode, out)
+    res = np.array(section, dtype=np.float32, order="C", copy=True)
+    if res.ndim != 2:
+        raise ValueError("section is [ntraces][nsamples]")
+    check(lib().p3d_despike_replace(int(device), _ptr(res), res.shape[0], res.shape[1], _ptr(spikes), spikes.shape[0], _ptr(level_start),
+                                    level_start.size - 1, DESPIKE_MODE[mode], DESPIKE_OUT[out], float(threshold)))
+    return res
+
+
+def despike_replace_dev(section, ntr, ns, spikes, level_start, mode, out, threshold, device=0):
+    """p3d_despike_replace_dev: ``section`` is a device pointer, rewritten in place; the records stay on the host."""
+    spikes, level_start = _despike_records(spikes, level_start, mode, out)
+    check(lib().p3d_despike_replace_dev(int(device), section, int(ntr), int(ns), _ptr(spikes), spikes.shape[0], _ptr(level_start),
+                                        level_start.size - 1, DESPIKE_MODE[mode], DESPIKE_OUT[out], float(threshold)))
 
 
 def _host_cube(x):

@@ -27,6 +27,7 @@
 
 #include "p3d.h"
 #include "p3d_internal.hpp"
+#include "p3d_sortnet.hpp"
 
 namespace {
 
@@ -88,26 +89,6 @@ __device__ inline float funkey(unsigned k)
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
-template <int N>
-__device__ inline void bitonic(float (&v)[N])
-{
-#pragma unroll
-    for (int k = 2; k <= N; k <<= 1)
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1)
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const float a = v[i], b = v[l];
-                    const float lo = fminf(a, b), hi = fmaxf(a, b);
-                    const bool up = (i & k) == 0;
-                    v[i] = up ? lo : hi;
-                    v[l] = up ? hi : lo;
-                }
-            }
-}
-
 // median of the k values of sample j (k <= N), +inf padded and sorted in registers; runtime ranks picked by compare, not by index
 template <int N>
 __device__ inline float median_small(const BinArgs& a, long long t0, int k, long long j)
@@ -118,7 +99,7 @@ __device__ inline float median_small(const BinArgs& a, long long t0, int k, long
         v[q] = INFINITY;
         if (q < k) v[q] = tap(a, a.trace_off[t0 + q] - a.sbase, a.trace_len[t0 + q], a.shift[t0 + q], j);
     }
-    bitonic<N>(v);
+    p3d::bitonic<N>(v);
     const int m2 = k >> 1, m1 = (k - 1) >> 1;
     float lo = 0.0f, hi = 0.0f;
 #pragma unroll

@@ -425,3 +425,14 @@ def filter_frequency(data: np.ndarray, freqs: list, fs: float, filter_type: str,
 bandpass_filter = partial(filter_frequency, filter_type='bandpass')
 lowpass_filter = partial(filter_frequency, filter_type='lowpass')
 highpass_filter = partial(filter_frequency, filter_type='highpass')
+
+
+def moving_window_2D(a, w, dx=1, dy=1, writeable=False):
+    """All windows of shape ``w`` = (rows, columns) over the last two axes of ``a`` with steps ``dy`` (rows) and ``dx`` (columns), as a
+    strided view of shape (..., (rows - w[0]) // dy + 1, (columns - w[1]) // dx + 1, w[0], w[1]) (reference: functions/filter.py,
+    ``moving_window_2D``; NumPy only -- step 8 itself runs on the GPU, functions/despike.py)."""
+    a = np.asarray(a)
+    w = tuple(w)
+    nrow, ncol = (a.shape[-2] - w[-2]) // dy + 1, (a.shape[-1] - w[-1]) // dx + 1
+    return np.lib.stride_tricks.as_strided(a, shape=a.shape[:-2] + (nrow, ncol) + w,
+                                           strides=a.strides[:-2] + (a.strides[-2] * dy, a.strides[-1] * dx) + a.strides[-2:], writeable=writeable)

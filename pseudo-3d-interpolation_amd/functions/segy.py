@@ -177,3 +177,26 @@ def write_segy(path, data, dt_ms, fmt=5, headers=None, text=''):
         f.write(binh.tobytes())
         f.write(rec.tobytes())
     return path
+
+
+def update_samples(path, data):
+    """Overwrite the samples of an existing SEG-Y file in place with ``data`` [ntraces][ns] (float), encoded in the file's own sample
+    format; the file, binary and trace headers are not touched.  IBM (1) and IEEE (5) floats and the integer formats are supported."""
+    src = SegyFile(path)
+    data = np.asarray(data, dtype=np.float32)
+    if data.shape != (src.ntraces, src.ns):
+        raise ValueError(f'{path}: holds {src.ntraces} traces of {src.ns} samples, got an array of shape {data.shape}')
+    start = TEXT_BYTES + BIN_BYTES + TEXT_BYTES * max(src.binary['ExtendedHeaders'], 0)
+    fmt, dtype = src.format, src._dtype
+    del src
+    mm = np.memmap(path, dtype, 'r+', offset=start, shape=(data.shape[0],))
+    if fmt == 1:
+        mm['data'] = ieee2ibm(data)
+    elif fmt == 5:
+        mm['data'] = data
+    else:
+        info = np.iinfo(np.dtype(SAMPLE_DTYPE[fmt]))
+        mm['data'] = np.clip(np.rint(data), info.min, info.max)
+    mm.flush()
+    del mm
+    return path
