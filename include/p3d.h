@@ -442,6 +442,39 @@ int p3d_despike_replace(int device, float* section, int ntr, int ns, const int* 
 int p3d_despike_replace_dev(int device, float* section_dev, int ntr, int ns, const int* spikes, size_t nspikes, const int* level_start, int nlevels, int mode,
                             int out, float threshold);
 
+/* ---- step 5: static correction of a 2-D section (p3d_static.hip; the reference's detect_seafloor_reflection / compensate_static) --------------
+ * The section is trace-major [ntr][ns] float32.  The valid slice of trace x is [0, ns) (padded = 0) or [max(first[x], 0), + nvalid) cut at the end
+ * of the trace (padded = 1: a zero-padded file); row numbers below count from the start of the slice.
+ *   scan:   first[x] = index of the first non-zero sample, -1 for a trace of zeros (such traces are left out of everything that follows:
+ *           peak 0, cross 0, peak_idx -1).
+ *   stalta: c = running sum of a^2 (double), sta = (c[i] - c[i - nsta]) / nsta (c[i] / nsta for i < nsta), lta alike, sta = 0 for i < nlta - 1,
+ *           ratio = sta / lta (0 where lta == 0); 1 <= nsta <= nlta <= P3D_STATIC_MAX_NLTA (larger: P3D_ERR_UNSUPPORTED).
+ *           max:   peak[x] = the largest ratio of rows nlta ... 2 nlta - 1 (0 when the slice has no such row);
+ *           cross: cross[x] = the first row whose ratio exceeds threshold (0 when none does).  The ratio is never stored.
+ *   peak:   window base[x] - win ... base[x] + win, clipped to the slice; the n largest (signed) amplitudes, equal ones by ascending position;
+ *           their positions ascending p[0] < p[1] < ..., the group p[:i] with i the first index where p[i + 1] - p[i] > 1 (p[:1] for i = 0, all
+ *           when there is no gap); peak_idx[x] = the position (row of the slice) of the largest amplitude of the group.  1 <= win <=
+ *           P3D_STATIC_MAX_WIN, 1 <= n <= 2 win + 1 (beyond: P3D_ERR_UNSUPPORTED); 0 <= base[x] < rows of the slice is the caller's duty
+ *           (a window that misses the slice altogether yields -1).
+ *   shift:  out[x][t] = in[x][t - shift[x]] where 0 <= t - shift[x] < ns, else 0; in and out must not overlap.
+ * The _dev entry points take DEVICE buffers and return after the kernels have finished; detect / peak / shift take HOST arrays.  detect = scan, then
+ * (when *threshold is NaN) max and *threshold = the largest peak of the live traces, then cross. */
+#define P3D_STATIC_MAX_WIN 255
+#define P3D_STATIC_MAX_NLTA 7680
+int p3d_static_scan_dev(int device, const float* section_dev, int ntr, int ns, int* first_dev);
+int p3d_static_stalta_max_dev(int device, const float* section_dev, int ntr, int ns, const int* first_dev, int padded, int nvalid, int nsta, int nlta,
+                              double* peak_dev);
+int p3d_static_stalta_cross_dev(int device, const float* section_dev, int ntr, int ns, const int* first_dev, int padded, int nvalid, int nsta, int nlta,
+                                double threshold, int* cross_dev);
+int p3d_static_peak_dev(int device, const float* section_dev, int ntr, int ns, const int* first_dev, int padded, int nvalid, const int* base_dev, int win,
+                        int n, int* peak_idx_dev);
+int p3d_static_shift_dev(int device, const float* in_dev, int ntr, int ns, const int* shift_dev, float* out_dev);
+int p3d_static_detect(int device, const float* section, int ntr, int ns, int padded, int nvalid, int nsta, int nlta, double* threshold, int* first,
+                      int* cross);
+int p3d_static_peak(int device, const float* section, int ntr, int ns, const int* first, int padded, int nvalid, const int* base, int win, int n,
+                    int* peak_idx);
+int p3d_static_shift(int device, const float* section, int ntr, int ns, const int* shift, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,16 @@ PROTOTYPES = {
     "p3d_despike_replace": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]),
     "p3d_despike_replace_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.c_float]),
+    "p3d_static_scan_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_static_stalta_max_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_static_stalta_cross_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                              C.c_void_p]),
+    "p3d_static_peak_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_static_shift_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_static_detect": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p,
+                                    C.c_void_p]),
+    "p3d_static_peak": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_static_shift": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1304,6 +1314,119 @@ def despike_replace_dev(section, ntr, ns, spikes, level_start, mode, out, thresh
     spikes, level_start = _despike_records(spikes, level_start, mode, out)
     check(lib().p3d_despike_replace_dev(int(device), section, int(ntr), int(ns), _ptr(spikes), spikes.shape[0], _ptr(level_start),
                                         level_start.size - 1, DESPIKE_MODE[mode], DESPIKE_OUT[out], float(threshold)))
+
+
+# ---- step 5: static correction (include/p3d.h, p3d_static.hip) ------------------------------------------------
+STATIC_MAX_WIN = 255         # P3D_STATIC_MAX_WIN of include/p3d.h
+STATIC_MAX_NLTA = 7680       # P3D_STATIC_MAX_NLTA
+
+
+def _static_windows(nsta, nlta):
+    nsta, nlta = int(nsta), int(nlta)
+    if nsta < 1 or nlta < nsta:
+        raise ValueError(f"the STA / LTA windows must satisfy 1 <= nsta <= nlta, got nsta={nsta}, nlta={nlta}")
+    if nlta > STATIC_MAX_NLTA:
+        raise UnsupportedError(P3D_ERR_UNSUPPORTED, f"long windows of up to {STATIC_MAX_NLTA} samples are supported, got {nlta}")
+    return nsta, nlta
+
+
+def _static_pick(win, n):
+    win, n = int(win), int(n)
+    if win < 1 or n < 1:
+        raise ValueError(f"the search window and the number of amplitudes must be at least 1, got win={win}, n={n}")
+    if win > STATIC_MAX_WIN:
+        raise UnsupportedError(P3D_ERR_UNSUPPORTED, f"search windows of up to +- {STATIC_MAX_WIN} samples are supported, got {win}")
+    if n > 2 * win + 1:
+        raise UnsupportedError(P3D_ERR_UNSUPPORTED, f"a window of {2 * win + 1} samples cannot give {n} amplitudes")
+    return win, n
+
+
+def _static_section(section):
+    section = np.ascontiguousarray(section, dtype=np.float32)
+    if section.ndim != 2 or section.size == 0:
+        raise ValueError("section is [ntraces][nsamples]")
+    return section
+
+
+def _static_slice(ns, nvalid):
+    """(padded, nvalid) as the library takes them; ``nvalid`` None: the whole trace."""
+    if nvalid is None:
+        return 0, int(ns)
+    if not 1 <= int(nvalid) <= ns:
+        raise ValueError(f"{nvalid} valid samples do not fit traces of {ns} samples")
+    return 1, int(nvalid)
+
+
+def static_scan_dev(section, ntr, ns, first, device=0):
+    """p3d_static_scan_dev on device pointers: ``first`` receives int32 [ntr], the first non-zero sample of every trace (-1: none)."""
+    check(lib().p3d_static_scan_dev(int(device), section, int(ntr), int(ns), first))
+
+
+def static_stalta_max_dev(section, ntr, ns, first, nsta, nlta, peak, nvalid=None, device=0):
+    """p3d_static_stalta_max_dev: ``peak`` receives float64 [ntr], the largest STA/LTA ratio of rows nlta ... 2 nlta - 1 of every live trace."""
+    nsta, nlta = _static_windows(nsta, nlta)
+    padded, nvalid = _static_slice(ns, nvalid)
+    check(lib().p3d_static_stalta_max_dev(int(device), section, int(ntr), int(ns), first, padded, nvalid, nsta, nlta, peak))
+
+
+def static_stalta_cross_dev(section, ntr, ns, first, nsta, nlta, threshold, cross, nvalid=None, device=0):
+    """p3d_static_stalta_cross_dev: ``cross`` receives int32 [ntr], the first row of the valid slice whose ratio exceeds ``threshold``."""
+    nsta, nlta = _static_windows(nsta, nlta)
+    padded, nvalid = _static_slice(ns, nvalid)
+    check(lib().p3d_static_stalta_cross_dev(int(device), section, int(ntr), int(ns), first, padded, nvalid, nsta, nlta, float(threshold), cross))
+
+
+def static_peak_dev(section, ntr, ns, first, base, win, n, out, nvalid=None, device=0):
+    """p3d_static_peak_dev: ``out`` receives int32 [ntr], the picked row of the valid slice (-1 for zero traces)."""
+    win, n = _static_pick(win, n)
+    padded, nvalid = _static_slice(ns, nvalid)
+    check(lib().p3d_static_peak_dev(int(device), section, int(ntr), int(ns), first, padded, nvalid, base, win, n, out))
+
+
+def static_shift_dev(section, ntr, ns, shift, out, device=0):
+    """p3d_static_shift_dev: out[x][t] = section[x][t - shift[x]] or 0; all device pointers, ``out`` another buffer than ``section``."""
+    check(lib().p3d_static_shift_dev(int(device), section, int(ntr), int(ns), shift, out))
+
+
+def static_detect(section, nsta, nlta, threshold=None, nvalid=None, device=0):
+    """Trace scan and both STA/LTA passes on a host section [ntr][ns] (p3d_static_detect).  Returns ``(first, threshold, cross)``: int32
+    [ntr] first non-zero sample (-1: zero trace), the threshold used (the one given, or the largest ratio of rows nlta ... 2 nlta - 1
+    over the live traces), int32 [ntr] first row of the valid slice whose ratio exceeds it."""
+    nsta, nlta = _static_windows(nsta, nlta)
+    section = _static_section(section)
+    ntr, ns = section.shape
+    padded, nvalid = _static_slice(ns, nvalid)
+    thr = C.c_double(float("nan") if threshold is None else float(threshold))
+    first, cross = np.empty(ntr, np.int32), np.empty(ntr, np.int32)
+    check(lib().p3d_static_detect(int(device), _ptr(section), ntr, ns, padded, nvalid, nsta, nlta, C.byref(thr), _ptr(first), _ptr(cross)))
+    return first, thr.value, cross
+
+
+def static_peak(section, first, base, win, n, nvalid=None, device=0):
+    """The peak pick on a host section [ntr][ns] (p3d_static_peak); ``first`` as `static_detect` returns it, ``base`` int32 [ntr] rows of the
+    valid slice.  Returns int32 [ntr] (-1 for zero traces)."""
+    win, n = _static_pick(win, n)
+    section = _static_section(section)
+    ntr, ns = section.shape
+    padded, nvalid = _static_slice(ns, nvalid)
+    first = np.ascontiguousarray(first, dtype=np.int32)
+    base = np.ascontiguousarray(base, dtype=np.int32)
+    if first.shape != (ntr,) or base.shape != (ntr,):
+        raise ValueError("one value per trace")
+    out = np.empty(ntr, np.int32)
+    check(lib().p3d_static_peak(int(device), _ptr(section), ntr, ns, _ptr(first), padded, nvalid, _ptr(base), win, n, _ptr(out)))
+    return out
+
+
+def static_shift(section, shift, device=0):
+    """Shift the traces of a host section [ntr][ns] by ``shift`` samples each (p3d_static_shift); returns the new section."""
+    section = _static_section(section)
+    shift = np.ascontiguousarray(shift, dtype=np.int32)
+    if shift.shape != (section.shape[0],):
+        raise ValueError("one shift per trace")
+    out = np.empty_like(section)
+    check(lib().p3d_static_shift(int(device), _ptr(section), section.shape[0], section.shape[1], _ptr(shift), _ptr(out)))
+    return out
 
 
 def _host_cube(x):

@@ -6,7 +6,8 @@ float), 2 (int32), 3 (int16), 5 (IEEE float) and 8 (int8).  The file is memory-m
 and samples are read without copying the file; samples are converted to float32 on access.
 
 Trace header fields (1-based byte positions, the ones step 10 scrapes): 1 TRACE_SEQUENCE_LINE, 5 TRACE_SEQUENCE_FILE, 9 FieldRecord,
-71 SourceGroupScalar, 73 SourceX, 77 SourceY, 109 DelayRecordingTime, 115 TRACE_SAMPLE_COUNT, 117 TRACE_SAMPLE_INTERVAL (microseconds)."""
+71 SourceGroupScalar, 73 SourceX, 77 SourceY, 109 DelayRecordingTime, 115 TRACE_SAMPLE_COUNT, 117 TRACE_SAMPLE_INTERVAL (microseconds); the ones
+step 5 reads and writes: 61 SourceWaterDepth, 69 ElevationScalar, 103 TotalStaticApplied, 233 UnassignedInt1, 237 UnassignedInt2."""
 import numpy as np
 
 TEXT_BYTES, BIN_BYTES, TRACE_HEADER_BYTES = 3200, 400, 240
@@ -16,17 +17,23 @@ TRACE_FIELDS = {
     'TRACE_SEQUENCE_LINE': (1, '>i4'),
     'TRACE_SEQUENCE_FILE': (5, '>i4'),
     'FieldRecord': (9, '>i4'),
+    'SourceWaterDepth': (61, '>i4'),
+    'ElevationScalar': (69, '>i2'),
     'SourceGroupScalar': (71, '>i2'),
     'SourceX': (73, '>i4'),
     'SourceY': (77, '>i4'),
+    'TotalStaticApplied': (103, '>i2'),
     'DelayRecordingTime': (109, '>i2'),
     'TRACE_SAMPLE_COUNT': (115, '>u2'),
     'TRACE_SAMPLE_INTERVAL': (117, '>u2'),
+    'UnassignedInt1': (233, '>i4'),
+    'UnassignedInt2': (237, '>i4'),
 }
 # binary header: name: (1-based byte in the file, dtype)
 BIN_FIELDS = {
     'Interval': (3217, '>u2'),
     'Samples': (3221, '>u2'),
+    'SamplesOriginal': (3223, '>u2'),
     'Format': (3225, '>i2'),
     'SEGYRevision': (3501, '>u2'),
     'TraceFlag': (3503, '>i2'),
@@ -143,10 +150,10 @@ def scaled_coordinates(scalar, x, y):
     return x * scalar, y * scalar
 
 
-def write_segy(path, data, dt_ms, fmt=5, headers=None, text=''):
+def write_segy(path, data, dt_ms, fmt=5, headers=None, text='', binary=None):
     """Write float samples ``data`` [ntraces][ns] as a SEG-Y file (revision 1, fixed-length traces).  ``headers``: optional dict of
     trace-header field arrays (TRACE_FIELDS names); TRACE_SEQUENCE_LINE / _FILE default to 1 ... n, sample count and interval to the
-    file's."""
+    file's.  ``binary``: optional dict of further binary-header values (BIN_FIELDS names, e.g. SamplesOriginal); all others are zero."""
     data = np.asarray(data, dtype=np.float32)
     if data.ndim != 2:
         raise ValueError('data is [ntraces][nsamples]')
@@ -168,7 +175,7 @@ def write_segy(path, data, dt_ms, fmt=5, headers=None, text=''):
         rec['data'] = np.clip(np.rint(data), info.min, info.max)
     txt = text.encode('cp500', 'replace')[:TEXT_BYTES].ljust(TEXT_BYTES, ' '.encode('cp500'))
     binh = np.zeros(BIN_BYTES, np.uint8)
-    for k, v in {'Interval': int(round(dt_ms * 1000)), 'Samples': ns, 'Format': fmt, 'SEGYRevision': 0x0100, 'TraceFlag': 1,
+    for k, v in {**(binary or {}), 'Interval': int(round(dt_ms * 1000)), 'Samples': ns, 'Format': fmt, 'SEGYRevision': 0x0100, 'TraceFlag': 1,
                  'ExtendedHeaders': 0}.items():
         b, dt = BIN_FIELDS[k]
         binh[b - 1 - TEXT_BYTES:b - 1 - TEXT_BYTES + np.dtype(dt).itemsize] = np.frombuffer(np.array(v, dt).tobytes(), np.uint8)
@@ -197,6 +204,32 @@ def update_samples(path, data):
     else:
         info = np.iinfo(np.dtype(SAMPLE_DTYPE[fmt]))
         mm['data'] = np.clip(np.rint(data), info.min, info.max)
+    mm.flush()
+    del mm
+    return path
+
+
+def update_headers(path, fields):
+    """Overwrite trace-header words of an existing SEG-Y file in place: ``fields`` maps TRACE_FIELDS names to one value per trace (or a
+    scalar for all traces).  Values must fit the field's width; samples and all other header bytes are not touched."""
+    src = SegyFile(path)
+    ntr, dtype = src.ntraces, src._dtype
+    start = TEXT_BYTES + BIN_BYTES + TEXT_BYTES * max(src.binary['ExtendedHeaders'], 0)
+    del src
+    columns = {}
+    for name, values in fields.items():
+        if name not in TRACE_FIELDS:
+            raise KeyError(f'{name!r} is not one of the trace-header fields {sorted(TRACE_FIELDS)}')
+        values = np.broadcast_to(np.asarray(values), (ntr,)) if np.ndim(values) == 0 else np.asarray(values)
+        if values.shape != (ntr,):
+            raise ValueError(f'{path}: holds {ntr} traces, got {values.shape} values for {name}')
+        info = np.iinfo(np.dtype(TRACE_FIELDS[name][1]))
+        if values.size and (values.min() < info.min or values.max() > info.max):
+            raise OverflowError(f'{name}: values outside the range of a {info.bits}-bit header word')
+        columns[name] = values
+    mm = np.memmap(path, dtype, 'r+', offset=start, shape=(ntr,))
+    for name, values in columns.items():
+        mm[name] = values
     mm.flush()
     del mm
     return path
