@@ -1593,6 +1593,15 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         HIP_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * 2048 * (size_t)nslices, p->stream));
     }
 
+    // The cost sums of the iterations (sum |x| per slice) decide the early exit and fill the caller's table.  A job with neither
+    // (eps = 0 and sums == NULL: the driver's bench line, sharding.pocs_block_on_device) cannot read them: its loop does not add the
+    // rows up, and the row passes of 1024-sample rows (row_pipe32_kernel) do not compute them -- 32 moduli, a shuffle reduction in
+    // double and a store per unit.  The iterate is the same bits; the first pass keeps its sums (p3d_pocs_prime_dev cannot know the job).
+    const bool no_sums = !early && sums == nullptr;
+    // rows of 1024 samples whose first pass wrote the compact samples in row_pipe32_kernel's order: that family all the way
+    // (r.xc is null whenever the first pass wrote none: non-binary mask, no compact samples wanted, energy at unobserved traces)
+    const bool fam32 = !real_path && p->use32 && r.xc != nullptr && r.bits32 != nullptr;
+    if (no_sums && fam32 && !adaptive) r.sums = nullptr;
     HIP_TRY(stamp());
     int last_finalized = 0;   // early exit: slices with done <= last_finalized have been handed to `out`
     // Debug mode of the invariant the deferred finalize rests on (RowArgs::only_done_lo, ColArgs::done): the work slice of a converged slice
@@ -1648,9 +1657,6 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         HIP_TRY(stamp());
         r.sum_row = k + 1;
         bool piped = false;
-        // rows of 1024 samples whose first pass wrote the compact samples in row_pipe32_kernel's order: that family all the way
-        // (r.xc is null whenever the first pass wrote none: non-binary mask, no compact samples wanted, energy at unobserved traces)
-        const bool fam32 = !real_path && p->use32 && r.xc != nullptr && r.bits32 != nullptr;
         if (real_path) {
             HIP_TRY(p->ops_row->row_real(k + 1 < niter ? REAL_MID : REAL_LAST, r, p->pipe_wgs, p->stream));
             piped = true;
@@ -1671,7 +1677,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         }
         if (!piped) HIP_TRY(p->ops_row->row(k + 1 < niter ? ROW_MID : ROW_LAST, r, p->stream));
         HIP_TRY(stamp());
-        reduce_rows_kernel<<<nslices, 256, 0, p->stream>>>(p->rowsum, p->sums + (size_t)(k + 1) * nslices, p->nil);
+        if (!no_sums) reduce_rows_kernel<<<nslices, 256, 0, p->stream>>>(p->rowsum, p->sums + (size_t)(k + 1) * nslices, p->nil);
         if (early) {
             conv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
             // slices that just finished are skipped from now on: their rows must read as zero afterwards

@@ -191,16 +191,28 @@ hipError_t launch_row_pipe32(int pm, const RowArgs& a, int cus, hipStream_t st)
         if ((e = allow_lds(row_pipe32_kernel<DT, SP, PM, AD>, lds)) != hipSuccess) return e;                    \
         row_pipe32_kernel<DT, SP, PM, AD><<<grid, P32::THREADS, lds, st>>>(a);                                  \
     } while (0)
-        const bool sp = a.nzl != nullptr, c64 = a.dtype == 0;
+        // the passes without the per-row sums of |x| (RowArgs::sums == nullptr; plain POCS, steady state and last pass)
+#define P3D_PIPE32_NS(DT, SP, PM)                                                                               \
+    do {                                                                                                        \
+        if ((e = allow_lds(row_pipe32_kernel<DT, SP, PM, false, false>, lds)) != hipSuccess) return e;          \
+        row_pipe32_kernel<DT, SP, PM, false, false><<<grid, P32::THREADS, lds, st>>>(a);                        \
+    } while (0)
+        const bool sp = a.nzl != nullptr, c64 = a.dtype == 0, sums = a.sums != nullptr;
         if (pm == PIPE_FIRST) {
             if (a.adaptive) { if (c64) P3D_PIPE32(0, false, PIPE_FIRST, true); else P3D_PIPE32(1, false, PIPE_FIRST, true); }
             else { if (c64) P3D_PIPE32(0, false, PIPE_FIRST, false); else P3D_PIPE32(1, false, PIPE_FIRST, false); }
+        } else if (pm == PIPE_LAST && !sums && !a.adaptive) {
+            if (c64) { if (sp) P3D_PIPE32_NS(0, true, PIPE_LAST); else P3D_PIPE32_NS(0, false, PIPE_LAST); }
+            else { if (sp) P3D_PIPE32_NS(1, true, PIPE_LAST); else P3D_PIPE32_NS(1, false, PIPE_LAST); }
         } else if (pm == PIPE_LAST) {
             if (c64) { if (sp) P3D_PIPE32(0, true, PIPE_LAST, false); else P3D_PIPE32(0, false, PIPE_LAST, false); }
             else { if (sp) P3D_PIPE32(1, true, PIPE_LAST, false); else P3D_PIPE32(1, false, PIPE_LAST, false); }
         } else if (pm == PIPE_MID && a.adaptive) {
             if (c64) { if (sp) P3D_PIPE32(0, true, PIPE_MID, true); else P3D_PIPE32(0, false, PIPE_MID, true); }
             else { if (sp) P3D_PIPE32(1, true, PIPE_MID, true); else P3D_PIPE32(1, false, PIPE_MID, true); }
+        } else if (pm == PIPE_MID && !sums) {
+            if (c64) { if (sp) P3D_PIPE32_NS(0, true, PIPE_MID); else P3D_PIPE32_NS(0, false, PIPE_MID); }
+            else { if (sp) P3D_PIPE32_NS(1, true, PIPE_MID); else P3D_PIPE32_NS(1, false, PIPE_MID); }
         } else if (pm == PIPE_MID) {
             if (c64) { if (sp) P3D_PIPE32(0, true, PIPE_MID, false); else P3D_PIPE32(0, false, PIPE_MID, false); }
             else { if (sp) P3D_PIPE32(1, true, PIPE_MID, false); else P3D_PIPE32(1, false, PIPE_MID, false); }
@@ -208,6 +220,7 @@ hipError_t launch_row_pipe32(int pm, const RowArgs& a, int cus, hipStream_t st)
             return hipErrorInvalidValue;
         }
 #undef P3D_PIPE32
+#undef P3D_PIPE32_NS
         return hipGetLastError();
     } else {
         return hipErrorNotSupported;

@@ -58,9 +58,12 @@ P3D_D void fft1024_32(c32 (&v)[32], c32* row, const c32* tw, int j)
     p32_half2<DIR>(v, row, tw, j);
 }
 
-template <int DT, bool SPARSE, int PM, bool ADAPT = false>
+// SUMS = false (PIPE_MID / PIPE_LAST, plain POCS): the per-row sums of |x| are neither computed nor stored -- for jobs that cannot read them
+// (no early exit and no cost table asked for: p3d_pocs_run_dev).  The iterate is the same bits: the sum is a side product of it.
+template <int DT, bool SPARSE, int PM, bool ADAPT = false, bool SUMS = true>
 __global__ __launch_bounds__(P32::THREADS, 2) void row_pipe32_kernel(const RowArgs a)
 {
+    static_assert(SUMS || (PM != PIPE_FIRST && !ADAPT), "the first pass and APOCS always keep the sums");
     constexpr int N = P32::N, PPT = 32, UPB = P32::UPB;
     constexpr unsigned ES = DT == 0 ? 8u : 4u;    // bytes per observed sample
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -297,7 +300,7 @@ __global__ __launch_bounds__(P32::THREADS, 2) void row_pipe32_kernel(const RowAr
         {   // (dropped stores: exact wait counts at the loop header, see the first pass)
 #pragma unroll
             for (int k = 0; k < PPT; ++k) v[k] = c32{0.f, 0.f};
-            buf_store_f64(sums_srd, BUF_OOB, 0u, 0.0);
+            if constexpr (SUMS) buf_store_f64(sums_srd, BUF_OOB, 0u, 0.0);   // (no sums: a trip issues one store less, and so does this edge)
             store_work(v, cur, false);
         }
         {
@@ -319,7 +322,7 @@ __global__ __launch_bounds__(P32::THREADS, 2) void row_pipe32_kernel(const RowAr
             // (the unit's mask words are fetched again here rather than carried from the request of its samples across both transforms:
             // 64 scalar registers held that long spill into vector lanes, a v_readlane per use)
             mask_words(mw_cur, cur);
-            float acc = 0.f;
+            [[maybe_unused]] float acc = 0.f;
             __amdgpu_buffer_rsrc_t wo_srd = sums_srd;
             unsigned wo_so = 0u, wo_vo = BUF_OOB;
             if constexpr (ADAPT && PM == PIPE_MID) {
@@ -335,7 +338,8 @@ __global__ __launch_bounds__(P32::THREADS, 2) void row_pipe32_kernel(const RowAr
                 const float w = obs ? w_obs : 1.0f;
                 // POCS.py:616-619 with the 1 / (N1 N2) of the inverse transform folded into the weight (one multiply per sample less)
                 c32 xn = axpby(v[k], obs ? ws_obs : a.scale, raw_c32(bx[k]), a.alpha);
-                acc += abs_c32(xn);
+                if constexpr (SUMS) acc += abs_c32(xn);
+                else asm volatile("" : "+v"(xn.x), "+v"(xn.y));   // (keeps the order of the registers the running sum imposed: without it the dense last pass spills)
                 if constexpr (ADAPT && PM == PIPE_MID) {
                     if (a.write_out) {
                         if (DT == 0) buf_store_c32(wo_srd, wo_vo, wo_so, xn);
@@ -355,7 +359,9 @@ __global__ __launch_bounds__(P32::THREADS, 2) void row_pipe32_kernel(const RowAr
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (!P3D_ABL_NOSUMS) store_row_sum(acc, cur);
+            if constexpr (SUMS) {
+                if (!P3D_ABL_NOSUMS) store_row_sum(acc, cur);
+            }
             __builtin_amdgcn_sched_barrier(0);
             // the next unit's work-buffer elements are requested BEFORE the forward transform, its observed samples behind it
             issue_work(by, nxt);
