@@ -475,6 +475,52 @@ int p3d_static_peak(int device, const float* section, int ntr, int ns, const int
                     int* peak_idx);
 int p3d_static_shift(int device, const float* section, int ntr, int ns, const int* shift, float* out);
 
+/* ---- step 7: mistie correction of crossing 2-D lines (p3d_mistie.hip; the reference's mistie_correction_segy.py) -----------------------------------
+ * Lines: all vertices (shot points) as doubles xy [nv][2] (x, y), line L owns vertices line_off[L] ... line_off[L + 1] - 1 (line_off: HOST, nlines + 1
+ * entries from 0 to nv, also in the _dev entry points: a small table); segment s of a line joins its vertices s and s + 1.
+ *   cross:   every point at which a segment of line i meets a segment of line j, for the line pairs (i, j), 0 <= i < j < nlines, of pairs [npairs][2]
+ *            (HOST; the caller keeps the pairs whose bounding boxes overlap).  A segment pair is a hit when it crosses properly, touches at an end
+ *            point or shares a vertex (the point is then that vertex, exactly); otherwise the point is A0 + t (A1 - A0) on line i's segment.  Collinear
+ *            overlapping segments give the two ends of the overlap (part 0 and 1; one point when they coincide).  Segments are taken in tiles of 64 and
+ *            tile pairs with disjoint bounding boxes are skipped.  Hits are appended IN NO DEFINED ORDER to hits[capacity]; *needed is the number of hits
+ *            found, which may exceed capacity (then the first `capacity` appended ones were stored: call again with a buffer of *needed).  One crossing
+ *            through a shared vertex of consecutive segments is found once per segment: callers sort by (pair, seg_i, seg_j, part) and drop repeated
+ *            points.
+ *   nearest: for crossing c at points[c] and side s in {0, 1}, the vertex of line lines[c][s] nearest to the point: index[c][s] (first minimum of
+ *            sqrt(dx^2 + dy^2) in double, the whole line is searched; -1 for a line without vertices or a line number out of range) and dist[c][s].
+ *   xcorr:   a, b float32 [ncross][ns]; ranges [ncross][4] = (first sample, length) of the window of a and of b.  Per crossing: the samples at which
+ *            either trace is exactly 0 are dropped, n remain; cc = scipy.signal.correlate(a, b, mode='same') by direct sums in double (lags
+ *            -(n / 2) ... n - 1 - n / 2); k = the first arg max of cc if |max| >= |min| else the first arg min; shift = n / 2 - k; coeff = Pearson's r
+ *            of the n samples (double; NaN when a trace is constant, n = 1 included).  status: 0 fine, P3D_MISTIE_EMPTY no sample left,
+ *            P3D_MISTIE_LENGTHS the two windows differ in length, P3D_MISTIE_RANGE a window outside the trace (or longer than max_len); shift, coeff
+ *            and n are 0 then.  path: AUTO keeps the compacted traces in LDS when the longest window has at most P3D_MISTIE_LDS_SAMPLES samples, else in
+ *            global memory (work: DEVICE [ncross][2][ns] floats, or NULL: allocated); LDS / GLOBAL force one form (LDS beyond the limit:
+ *            P3D_ERR_UNSUPPORTED).  Both forms give identical results.  max_len (_dev only): the longest window of the batch.
+ * Applying a line's offset needs no entry of its own: p3d_static_shift with one shift for all traces. */
+#define P3D_MISTIE_LDS_SAMPLES 8064
+#define P3D_MISTIE_PATH_AUTO 0
+#define P3D_MISTIE_PATH_LDS 1
+#define P3D_MISTIE_PATH_GLOBAL 2
+#define P3D_MISTIE_EMPTY 1
+#define P3D_MISTIE_LENGTHS 2
+#define P3D_MISTIE_RANGE 3
+typedef struct p3d_mistie_hit {
+    int32_t pair, seg_i, seg_j, part;
+    double x, y;
+} p3d_mistie_hit;
+int p3d_mistie_cross_dev(int device, const double* xy_dev, const long long* line_off, int nlines, const int* pairs, int npairs, p3d_mistie_hit* hits_dev,
+                         size_t capacity, size_t* needed);
+int p3d_mistie_nearest_dev(int device, const double* xy_dev, const long long* line_off, int nlines, const double* points_dev, const int* lines_dev,
+                           size_t ncross, int* index_dev, double* dist_dev);
+int p3d_mistie_xcorr_dev(int device, const float* a_dev, const float* b_dev, size_t ncross, int ns, const int* ranges_dev, int max_len, int path,
+                         float* work_dev, int* shift_dev, double* coeff_dev, int* n_dev, int* status_dev);
+int p3d_mistie_cross(int device, const double* xy, const long long* line_off, int nlines, const int* pairs, int npairs, p3d_mistie_hit* hits, size_t capacity,
+                     size_t* needed);
+int p3d_mistie_nearest(int device, const double* xy, const long long* line_off, int nlines, const double* points, const int* lines, size_t ncross, int* index,
+                       double* dist);
+int p3d_mistie_xcorr(int device, const float* a, const float* b, size_t ncross, int ns, const int* ranges, int path, int* shift, double* coeff, int* n,
+                     int* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,14 @@ PROTOTYPES = {
                                     C.c_void_p]),
     "p3d_static_peak": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "p3d_static_shift": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_mistie_cross_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "p3d_mistie_nearest_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "p3d_mistie_xcorr_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3d_mistie_cross": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "p3d_mistie_nearest": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "p3d_mistie_xcorr": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1427,6 +1435,114 @@ def static_shift(section, shift, device=0):
     out = np.empty_like(section)
     check(lib().p3d_static_shift(int(device), _ptr(section), section.shape[0], section.shape[1], _ptr(shift), _ptr(out)))
     return out
+
+
+# ---- step 7: mistie correction (include/p3d.h, p3d_mistie.hip) ---------------------------------------------------
+MISTIE_LDS_SAMPLES = 8064    # P3D_MISTIE_LDS_SAMPLES of include/p3d.h
+MISTIE_PATH = {"auto": 0, "lds": 1, "global": 2}
+MISTIE_OK, MISTIE_EMPTY, MISTIE_LENGTHS, MISTIE_RANGE = 0, 1, 2, 3
+MISTIE_HIT = np.dtype([("pair", np.int32), ("seg_i", np.int32), ("seg_j", np.int32), ("part", np.int32), ("x", np.float64), ("y", np.float64)])
+
+
+def _mistie_lines(xy, line_off):
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+    line_off = np.ascontiguousarray(line_off, dtype=np.int64)
+    if line_off.ndim != 1 or line_off.size < 2 or line_off[0] != 0 or line_off[-1] != xy.shape[0] or np.any(np.diff(line_off) < 0):
+        raise ValueError("line_off holds nlines + 1 ascending vertex offsets from 0 to the number of vertices")
+    return xy, line_off
+
+
+def _mistie_pairs(pairs, nlines):
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= nlines or np.any(pairs[:, 0] >= pairs[:, 1])):
+        raise ValueError(f"line pairs are (i, j) with 0 <= i < j < {nlines}")
+    return pairs
+
+
+def mistie_cross_dev(xy, line_off, pairs, hits, capacity, device=0):
+    """p3d_mistie_cross_dev: ``xy`` and ``hits`` (``capacity`` records of `MISTIE_HIT`) are device pointers, ``line_off`` / ``pairs`` host arrays.
+    Returns the number of hits found (more than ``capacity``: only that many were stored); the records come in no defined order."""
+    line_off = np.ascontiguousarray(line_off, dtype=np.int64)
+    pairs = _mistie_pairs(pairs, line_off.size - 1)
+    needed = C.c_size_t(0)
+    check(lib().p3d_mistie_cross_dev(int(device), xy, _ptr(line_off), line_off.size - 1, _ptr(pairs), pairs.shape[0], hits, int(capacity), C.byref(needed)))
+    return needed.value
+
+
+def mistie_cross(xy, line_off, pairs, capacity=None, device=0):
+    """Every point at which a segment of line i meets one of line j for the (i, j) of ``pairs`` (p3d_mistie_cross), as a `MISTIE_HIT` record array
+    sorted by (pair, seg_i, seg_j, part), without the repeats of one point within a pair (a crossing through a shared vertex of consecutive
+    segments is found once per segment).  ``capacity``: records of the first attempt (default: 4 per pair, at least 1024); when more are
+    found the call is repeated ONCE with the number the first attempt reports."""
+    xy, line_off = _mistie_lines(xy, line_off)
+    pairs = _mistie_pairs(pairs, line_off.size - 1)
+    cap = max(1024, 4 * pairs.shape[0]) if capacity is None else int(capacity)
+    if cap < 0:
+        raise ValueError("capacity must not be negative")
+    needed = C.c_size_t(0)
+    for _ in range(2):
+        hits = np.zeros(max(cap, 1), MISTIE_HIT)
+        check(lib().p3d_mistie_cross(int(device), _ptr(xy), _ptr(line_off), line_off.size - 1, _ptr(pairs), pairs.shape[0], _ptr(hits), cap, C.byref(needed)))
+        if needed.value <= cap:
+            break
+        cap = needed.value
+    else:
+        raise P3DError(P3D_ERR_INVALID, f"the second attempt found {needed.value} hits, the first had reported {cap}")
+    hits = hits[:needed.value]
+    hits = hits[np.lexsort((hits["part"], hits["seg_j"], hits["seg_i"], hits["pair"]))]
+    keep = np.ones(hits.size, bool)
+    seen = set()
+    for k, h in enumerate(hits):                                  # first occurrence of a point within its pair
+        key = (int(h["pair"]), float(h["x"]), float(h["y"]))
+        keep[k] = key not in seen
+        seen.add(key)
+    return hits[keep]
+
+
+def mistie_nearest_dev(xy, line_off, points, lines, ncross, index, dist, device=0):
+    """p3d_mistie_nearest_dev: device pointers but ``line_off`` (host); ``index`` int32 [ncross][2], ``dist`` float64 [ncross][2]."""
+    line_off = np.ascontiguousarray(line_off, dtype=np.int64)
+    check(lib().p3d_mistie_nearest_dev(int(device), xy, _ptr(line_off), line_off.size - 1, points, lines, int(ncross), index, dist))
+
+
+def mistie_nearest(xy, line_off, points, lines, device=0):
+    """For every crossing ``points[c]`` and both of its lines ``lines[c]``: (index int32 [k][2], distance float64 [k][2]) of the nearest vertex,
+    the first minimum over the whole line (p3d_mistie_nearest)."""
+    xy, line_off = _mistie_lines(xy, line_off)
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+    lines = np.ascontiguousarray(lines, dtype=np.int32).reshape(-1, 2)
+    if lines.shape != points.shape:
+        raise ValueError("one pair of lines per crossing")
+    if lines.size and (lines.min() < 0 or lines.max() >= line_off.size - 1):
+        raise ValueError(f"line numbers run from 0 to {line_off.size - 2}")
+    index, dist = np.empty(lines.shape, np.int32), np.empty(lines.shape, np.float64)
+    check(lib().p3d_mistie_nearest(int(device), _ptr(xy), _ptr(line_off), line_off.size - 1, _ptr(points), _ptr(lines), points.shape[0], _ptr(index),
+                                   _ptr(dist)))
+    return index, dist
+
+
+def mistie_xcorr_dev(a, b, ncross, ns, ranges, max_len, shift, coeff, n, status, path="auto", work=None, device=0):
+    """p3d_mistie_xcorr_dev on device pointers (``work``: [ncross][2][ns] floats for the global-memory form, None: allocated)."""
+    check(lib().p3d_mistie_xcorr_dev(int(device), a, b, int(ncross), int(ns), ranges, int(max_len), MISTIE_PATH[path], work, shift, coeff, n, status))
+
+
+def mistie_xcorr(a, b, ranges, path="auto", device=0):
+    """Windowed cross-correlation of the trace pairs ``a[c]``, ``b[c]`` (float32 [ncross][ns]) over ``ranges[c] = (a first, a length, b first,
+    b length)`` (p3d_mistie_xcorr).  Returns ``(shift int32, coeff float64, n int32, status int32)`` per crossing; see include/p3d.h."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.ndim != 2 or a.shape != b.shape or a.shape[1] < 1:
+        raise ValueError("a and b are [ncross][nsamples], of one shape")
+    ranges = np.ascontiguousarray(ranges, dtype=np.int32).reshape(-1, 4)
+    if ranges.shape[0] != a.shape[0]:
+        raise ValueError("one (a first, a length, b first, b length) per crossing")
+    if path not in MISTIE_PATH:
+        raise ValueError(f"path is one of {sorted(MISTIE_PATH)}")
+    k = a.shape[0]
+    shift, coeff, n, status = np.zeros(k, np.int32), np.zeros(k, np.float64), np.zeros(k, np.int32), np.zeros(k, np.int32)
+    check(lib().p3d_mistie_xcorr(int(device), _ptr(a), _ptr(b), k, a.shape[1], _ptr(ranges), MISTIE_PATH[path], _ptr(shift), _ptr(coeff), _ptr(n),
+                                 _ptr(status)))
+    return shift, coeff, n, status
 
 
 def _host_cube(x):
