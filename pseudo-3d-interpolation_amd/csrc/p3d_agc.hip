@@ -19,34 +19,15 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
 #include "p3d.h"
-#include "p3d_internal.hpp"
+#include "p3d_host.hpp"
+
+using p3d::DevBuf;
+using p3d::fail;
+using p3d::use_device;
 
 namespace {
-
-int afail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define A_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return afail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
 
 enum { AGC_RMS = 0, AGC_MEAN = 1, AGC_MEDIAN = 2 };
 
@@ -184,68 +165,62 @@ extern "C" {
 
 int p3d_agc(int device, const float* x, size_t nt, size_t ntraces, int win, int kind, int squared, float* out, float* gain)
 {
-    if (!x || !out) return afail(P3D_ERR_INVALID, "NULL buffer");
-    if (nt < 1 || ntraces < 1) return afail(P3D_ERR_INVALID, "bad shape (nt %zu, ntraces %zu)", nt, ntraces);
-    if (win < 1) return afail(P3D_ERR_INVALID, "window of %d samples", win);
-    if (kind != AGC_RMS && kind != AGC_MEAN && kind != AGC_MEDIAN) return afail(P3D_ERR_INVALID, "unknown AGC kind %d", kind);
+    if (!x || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (nt < 1 || ntraces < 1) return fail(P3D_ERR_INVALID, "bad shape (nt %zu, ntraces %zu)", nt, ntraces);
+    if (win < 1) return fail(P3D_ERR_INVALID, "window of %d samples", win);
+    if (kind != AGC_RMS && kind != AGC_MEAN && kind != AGC_MEDIAN) return fail(P3D_ERR_INVALID, "unknown AGC kind %d", kind);
     if (win % 2 == 0) ++win;
     const int h = win / 2;
-    int ndev = 0;
-    A_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return afail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    A_TRY(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
 
     // traces per chunk: input, output (and gain) of a chunk within half of the free device memory
     size_t free_b = 0, total_b = 0;
-    A_TRY(hipMemGetInfo(&free_b, &total_b));
+    P3D_TRY(hipMemGetInfo(&free_b, &total_b));
     const size_t per_trace = nt * sizeof(float) * (gain ? 3 : 2);
     size_t chunk = (free_b / 2) / per_trace;
     if (chunk > ntraces) chunk = ntraces;
     if (chunk >= 256 && chunk < ntraces) chunk -= chunk % 256;
-    if (chunk < 1) return afail(P3D_ERR_UNSUPPORTED, "a trace of %zu samples does not fit in device memory", nt);
+    if (chunk < 1) return fail(P3D_ERR_UNSUPPORTED, "a trace of %zu samples does not fit in device memory", nt);
 
     DevBuf din, dout, dgain;
-    A_TRY(hipMalloc(&din.p, sizeof(float) * nt * chunk));
-    A_TRY(hipMalloc(&dout.p, sizeof(float) * nt * chunk));
-    if (gain) A_TRY(hipMalloc(&dgain.p, sizeof(float) * nt * chunk));
+    P3D_TRY(hipMalloc(&din.p, sizeof(float) * nt * chunk));
+    P3D_TRY(hipMalloc(&dout.p, sizeof(float) * nt * chunk));
+    if (gain) P3D_TRY(hipMalloc(&dgain.p, sizeof(float) * nt * chunk));
     const size_t pitch = ntraces * sizeof(float);
     for (size_t j0 = 0; j0 < ntraces; j0 += chunk) {
         const size_t n = ntraces - j0 < chunk ? ntraces - j0 : chunk;   // traces of this chunk: [nt][n] on the device
         const size_t w = n * sizeof(float);
-        A_TRY(hipMemcpy2D(din.p, w, x + j0, pitch, w, nt, hipMemcpyHostToDevice));
+        P3D_TRY(hipMemcpy2D(din.p, w, x + j0, pitch, w, nt, hipMemcpyHostToDevice));
         const unsigned blocks = (unsigned)((n + 255) / 256);
         if (kind == AGC_MEDIAN)
             agc_median_kernel<<<blocks, 256>>>((const float*)din.p, (float*)dout.p, (float*)dgain.p, (long long)nt, (long long)n, h, squared);
         else
             agc_sum_kernel<<<blocks, 256>>>((const float*)din.p, (float*)dout.p, (float*)dgain.p, (long long)nt, (long long)n, h, win, kind, squared);
-        A_TRY(hipGetLastError());
-        A_TRY(hipMemcpy2D(out + j0, pitch, dout.p, w, w, nt, hipMemcpyDeviceToHost));
-        if (gain) A_TRY(hipMemcpy2D(gain + j0, pitch, dgain.p, w, w, nt, hipMemcpyDeviceToHost));
+        P3D_TRY(hipGetLastError());
+        P3D_TRY(hipMemcpy2D(out + j0, pitch, dout.p, w, w, nt, hipMemcpyDeviceToHost));
+        if (gain) P3D_TRY(hipMemcpy2D(gain + j0, pitch, dgain.p, w, w, nt, hipMemcpyDeviceToHost));
     }
-    A_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_agc_dev(int device, const float* x, size_t nt, size_t ntraces, int win, int kind, int squared, float* out, float* gain)
 {
-    if (!x || !out) return afail(P3D_ERR_INVALID, "NULL buffer");
-    if (x == out) return afail(P3D_ERR_INVALID, "x and out must be different buffers");
-    if (nt < 1 || ntraces < 1) return afail(P3D_ERR_INVALID, "bad shape (nt %zu, ntraces %zu)", nt, ntraces);
-    if (win < 1) return afail(P3D_ERR_INVALID, "window of %d samples", win);
-    if (kind != AGC_RMS && kind != AGC_MEAN && kind != AGC_MEDIAN) return afail(P3D_ERR_INVALID, "unknown AGC kind %d", kind);
+    if (!x || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (x == out) return fail(P3D_ERR_INVALID, "x and out must be different buffers");
+    if (nt < 1 || ntraces < 1) return fail(P3D_ERR_INVALID, "bad shape (nt %zu, ntraces %zu)", nt, ntraces);
+    if (win < 1) return fail(P3D_ERR_INVALID, "window of %d samples", win);
+    if (kind != AGC_RMS && kind != AGC_MEAN && kind != AGC_MEDIAN) return fail(P3D_ERR_INVALID, "unknown AGC kind %d", kind);
     if (win % 2 == 0) ++win;
     const int h = win / 2;
-    int ndev = 0;
-    A_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return afail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    A_TRY(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
     const unsigned blocks = (unsigned)((ntraces + 255) / 256);
     if (kind == AGC_MEDIAN)
         agc_median_kernel<<<blocks, 256>>>(x, out, gain, (long long)nt, (long long)ntraces, h, squared);
     else
         agc_sum_kernel<<<blocks, 256>>>(x, out, gain, (long long)nt, (long long)ntraces, h, win, kind, squared);
-    A_TRY(hipGetLastError());
-    A_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 

@@ -5,8 +5,6 @@
 #include <climits>
 #include <cmath>
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -15,6 +13,7 @@
 
 #include "p3d.h"
 #include "p3d_generic.hpp"
+#include "p3d_host.hpp"
 #include "p3d_internal.hpp"
 #include "p3d_flex.hpp"
 #include "p3d_mix_entry.hpp"
@@ -309,25 +308,8 @@ static __global__ void pack_mask32_kernel(const uint16_t* bits, unsigned long lo
 
 static thread_local std::string g_err;
 
-static int fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-// the other translation units report through the same thread-local string (p3d_internal.hpp)
+// every translation unit reports through this thread-local string (p3d::fail, p3d_host.hpp)
 namespace p3d { void set_last_error(const char* msg) { g_err = msg; } }
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) return fail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 struct p3d_plan {
     int device = 0;
@@ -410,8 +392,8 @@ static int upload_table(p3d_plan* p, const LineOps* ops, bool for_rows, int n, c
         if (for_rows) ops->build_row_tw(host.data());
         else ops->build_col_tw(host.data());
     }
-    HIP_TRY(hipMalloc((void**)dst, sizeof(c32) * host.size()));
-    HIP_TRY(hipMemcpy(*dst, host.data(), sizeof(c32) * host.size(), hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc((void**)dst, sizeof(c32) * host.size()));
+    P3D_TRY(hipMemcpy(*dst, host.data(), sizeof(c32) * host.size(), hipMemcpyHostToDevice));
     return P3D_OK;
 }
 
@@ -427,7 +409,7 @@ int p3d_runtime_info(int* compiled_hip_version, int* runtime_hip_version)
 {
     if (!compiled_hip_version || !runtime_hip_version) return fail(P3D_ERR_INVALID, "NULL argument");
     *compiled_hip_version = HIP_VERSION;
-    HIP_TRY(hipRuntimeGetVersion(runtime_hip_version));
+    P3D_TRY(hipRuntimeGetVersion(runtime_hip_version));
     return P3D_OK;
 }
 
@@ -435,7 +417,7 @@ int p3d_device_count(int* n)
 {
     if (!n) return fail(P3D_ERR_INVALID, "n is NULL");
     *n = 0;
-    HIP_TRY(hipGetDeviceCount(n));
+    P3D_TRY(hipGetDeviceCount(n));
     return P3D_OK;
 }
 
@@ -480,10 +462,7 @@ static int create_plan(p3d_plan** out, int device, int nil, int nxl, int max_sli
     const bool generic = !oc || !orow || force_generic;
     if (generic && !(generic_ok(nil) && generic_ok(nxl)))
         return fail(P3D_ERR_UNSUPPORTED, "slice shape %d x %d: extents up to %d are supported", nil, nxl, GEN_MAX_N);
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = use_device(device)) return rc;
 
     p3d_plan* p = new p3d_plan;
     p->device = device;
@@ -504,7 +483,7 @@ static int create_plan(p3d_plan** out, int device, int nil, int nxl, int max_sli
         const int ct = is_flex(oc) ? flex_col_tile(nil) : oc->col_tile;
         p->tiles = (nxl + ct - 1) / ct;
         hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device));
+        P3D_TRY(hipGetDeviceProperties(&prop, device));
         p->cus = prop.multiProcessorCount;
         p->pipe_wgs = (orow->tpl > 0 && orow->tpl <= 256 && !getenv("P3D_NO_PIPE")) ? p->cus : 0;  // the launcher sizes the grid per variant
     }
@@ -597,8 +576,8 @@ int p3d_plan_create(p3d_plan** out, int device, int nil, int nxl, int max_slices
 int p3d_malloc(p3d_plan* p, void** dptr, size_t bytes)
 {
     if (!p || !dptr) return fail(P3D_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMalloc(dptr, bytes));
+    P3D_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipMalloc(dptr, bytes));
     return P3D_OK;
 }
 
@@ -606,22 +585,22 @@ int p3d_free(p3d_plan* p, void* dptr)
 {
     // p3d_malloc is a bare hipMalloc: the buffer does not die with its plan, so it can (and must) be freed after the plan is gone
     // too -- `p` may be NULL then (hipFree finds the owning device from the pointer)
-    if (p) HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipFree(dptr));
+    if (p) P3D_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipFree(dptr));
     return P3D_OK;
 }
 
 int p3d_dev_malloc(int device, void** dptr, size_t bytes)
 {
     if (!dptr) return fail(P3D_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc(dptr, bytes));
+    if (int rc = use_device(device)) return rc;
+    P3D_TRY(hipMalloc(dptr, bytes));
     return P3D_OK;
 }
 
 int p3d_dev_free(void* dptr)
 {
-    HIP_TRY(hipFree(dptr));
+    P3D_TRY(hipFree(dptr));
     return P3D_OK;
 }
 
@@ -630,9 +609,9 @@ int p3d_dev_memcpy(int device, void* dst, const void* src, size_t bytes, int kin
     if (kind < 0 || kind > 2) return fail(P3D_ERR_INVALID, "kind must be 0 (h2d), 1 (d2h) or 2 (d2d)");
     if (!bytes) return P3D_OK;
     if (!dst || !src) return fail(P3D_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMemcpy(dst, src, bytes, kind == 0 ? hipMemcpyHostToDevice : kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
-    if (kind == 2) HIP_TRY(hipDeviceSynchronize());   // (device-to-device copies return before they have run)
+    P3D_TRY(hipSetDevice(device));
+    P3D_TRY(hipMemcpy(dst, src, bytes, kind == 0 ? hipMemcpyHostToDevice : kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    if (kind == 2) P3D_TRY(hipDeviceSynchronize());   // (device-to-device copies return before they have run)
     return P3D_OK;
 }
 
@@ -640,37 +619,37 @@ int p3d_dev_memset(int device, void* dptr, int value, size_t bytes)
 {
     if (!bytes) return P3D_OK;
     if (!dptr) return fail(P3D_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMemset(dptr, value, bytes));
-    HIP_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipSetDevice(device));
+    P3D_TRY(hipMemset(dptr, value, bytes));
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_dev_synchronize(int device)
 {
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipSetDevice(device));
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_dev_mem_info(int device, size_t* free_bytes, size_t* total_bytes)
 {
     if (!free_bytes || !total_bytes) return fail(P3D_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMemGetInfo(free_bytes, total_bytes));
+    if (int rc = use_device(device)) return rc;
+    P3D_TRY(hipMemGetInfo(free_bytes, total_bytes));
     return P3D_OK;
 }
 
 int p3d_host_alloc(void** hptr, size_t bytes)
 {
     if (!hptr) return fail(P3D_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipHostMalloc(hptr, bytes, hipHostMallocDefault));
+    P3D_TRY(hipHostMalloc(hptr, bytes, hipHostMallocDefault));
     return P3D_OK;
 }
 
 int p3d_host_free(void* hptr)
 {
-    HIP_TRY(hipHostFree(hptr));
+    P3D_TRY(hipHostFree(hptr));
     return P3D_OK;
 }
 
@@ -681,18 +660,18 @@ int p3d_host_free(void* hptr)
 int p3d_memcpy_h2d(p3d_plan* p, void* dst, const void* src, size_t bytes)
 {
     if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     return P3D_OK;
 }
 
 int p3d_memcpy_d2h(p3d_plan* p, void* dst, const void* src, size_t bytes)
 {
     if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
-    HIP_TRY(hipSetDevice(p->device));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     return P3D_OK;
 }
 
@@ -714,7 +693,7 @@ int p3d_host_register(void* hptr, size_t bytes)
 int p3d_host_unregister(void* hptr)
 {
     if (!hptr) return fail(P3D_ERR_INVALID, "NULL argument");
-    HIP_TRY(hipHostUnregister(hptr));
+    P3D_TRY(hipHostUnregister(hptr));
     return P3D_OK;
 }
 
@@ -784,9 +763,9 @@ static int ensure_staging(p3d_plan* p, size_t bytes_per_cube)
     if (p->st_out) hipFree(p->st_out);
     p->st_x = p->st_out = nullptr;
     p->st_cap = 0;
-    HIP_TRY(hipMalloc(&p->st_x, bytes_per_cube));
-    HIP_TRY(hipMalloc(&p->st_out, bytes_per_cube));
-    if (!p->st_mask) HIP_TRY(hipMalloc((void**)&p->st_mask, sizeof(float) * p->slice_elems()));
+    P3D_TRY(hipMalloc(&p->st_x, bytes_per_cube));
+    P3D_TRY(hipMalloc(&p->st_out, bytes_per_cube));
+    if (!p->st_mask) P3D_TRY(hipMalloc((void**)&p->st_mask, sizeof(float) * p->slice_elems()));
     p->st_cap = bytes_per_cube;
     return P3D_OK;
 }
@@ -797,11 +776,11 @@ static int gen_fft2(p3d_plan* p, const c32* in, c32* out, int nslices, int inver
 {
     const float scale = (float)(1.0 / ((double)p->nil * (double)p->nxl));
     if (!inverse) {
-        HIP_TRY(gen_launch_line_fft(in, out, p->tw_row, p->grow, FWD, 1.0f, nslices, p->nil, p->nxl, true, done, p->stream));
-        HIP_TRY(gen_launch_line_fft(out, out, p->tw_col, p->gcol, FWD, 1.0f, nslices, p->nil, p->nxl, false, done, p->stream));
+        P3D_TRY(gen_launch_line_fft(in, out, p->tw_row, p->grow, FWD, 1.0f, nslices, p->nil, p->nxl, true, done, p->stream));
+        P3D_TRY(gen_launch_line_fft(out, out, p->tw_col, p->gcol, FWD, 1.0f, nslices, p->nil, p->nxl, false, done, p->stream));
     } else {
-        HIP_TRY(gen_launch_line_fft(in, out, p->tw_col, p->gcol, INV, 1.0f, nslices, p->nil, p->nxl, false, done, p->stream));
-        HIP_TRY(gen_launch_line_fft(out, out, p->tw_row, p->grow, INV, scale, nslices, p->nil, p->nxl, true, done, p->stream));
+        P3D_TRY(gen_launch_line_fft(in, out, p->tw_col, p->gcol, INV, 1.0f, nslices, p->nil, p->nxl, false, done, p->stream));
+        P3D_TRY(gen_launch_line_fft(out, out, p->tw_row, p->grow, INV, scale, nslices, p->nil, p->nxl, true, done, p->stream));
     }
     return P3D_OK;
 }
@@ -810,8 +789,8 @@ static int reduce_partials(p3d_plan* p, int nslices, double* stats, int tiles = 
 {
     if (tiles <= 0) tiles = p->tiles;
     std::vector<float> part((size_t)STATS_PARTIAL * tiles * nslices);
-    HIP_TRY(hipMemcpyAsync(part.data(), p->partials, sizeof(float) * part.size(), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpyAsync(part.data(), p->partials, sizeof(float) * part.size(), hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     for (int s = 0; s < nslices; ++s) {
         double lr = -INFINITY, li = -INFINITY, mx = 0.0, mn = INFINITY, sq = 0.0;
         for (int t = 0; t < tiles; ++t) {
@@ -834,7 +813,7 @@ static int fft2_enqueue(p3d_plan* p, const void* in, void* out, int nslices, int
     int rc = check_batch(p, nslices);
     if (rc) return rc;
     if (!in || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
     if (p->generic) {
         return gen_fft2(p, (const c32*)in, (c32*)out, nslices, inverse, nullptr);
     }
@@ -843,24 +822,24 @@ static int fft2_enqueue(p3d_plan* p, const void* in, void* out, int nslices, int
         r.x = in;
         r.work = p->work;
         r.dtype = P3D_C64;
-        HIP_TRY(first_row_pass(p, r));   // (every forward transform of a plan takes the same row pass: the same bits as the statistics and the loop)
+        P3D_TRY(first_row_pass(p, r));   // (every forward transform of a plan takes the same row pass: the same bits as the statistics and the loop)
         ColArgs c = col_args(p, nslices);
         c.in = p->work;
         c.out = (c32*)out;
         c.out_std = 1;
-        HIP_TRY(p->ops_col->col(COL_FWD, c, p->stream));
+        P3D_TRY(p->ops_col->col(COL_FWD, c, p->stream));
     } else {
         ColArgs c = col_args(p, nslices);
         c.in = (const c32*)in;
         c.in_std = 1;
         c.out = p->work;
-        HIP_TRY(p->ops_col->col(COL_INV, c, p->stream));
+        P3D_TRY(p->ops_col->col(COL_INV, c, p->stream));
         RowArgs r = row_args(p, nslices);
         r.work = p->work;
         r.out = out;
         r.dtype = P3D_C64;
         r.plain = 1;
-        HIP_TRY(p->ops_row->row(ROW_LAST, r, p->stream));
+        P3D_TRY(p->ops_row->row(ROW_LAST, r, p->stream));
     }
     return P3D_OK;
 }
@@ -890,7 +869,7 @@ int shearlet_spread_inv(p3d_plan* p, const c32* F, const float* psi, int nb, int
     r.x = F;
     r.work = p->work;
     r.sh = shear_args(psi, nullptr, nsh, 0, 0, 0, 0, sup, sup_words, pair);
-    HIP_TRY(p->ops_row->row(ROW_SPREAD_INV, r, p->stream));
+    P3D_TRY(p->ops_row->row(ROW_SPREAD_INV, r, p->stream));
     return P3D_OK;
 }
 
@@ -907,12 +886,12 @@ int shearlet_col_shrink(p3d_plan* p, const c32* tau, int nb, int nsh, int niter,
     hipError_t ce = hipErrorNotSupported;
     if (pair) {   // two columns per transform on Hermitian work slices: the other two passes ran / will run on half the rows, no way back
         if (!real_only || !shearlet_pair_supported(p)) return fail(P3D_ERR_INVALID, "the paired column pass does not apply to this plan");
-        HIP_TRY(p->ops_col->col_shear_pair(c, p->stream));
+        P3D_TRY(p->ops_col->col_shear_pair(c, p->stream));
         return P3D_OK;
     }
     if (!p->no_colpipe && p->cus > 0 && p->ops_col->col_pipe != nullptr && p->ops_col->n >= 2048) ce = p->ops_col->col_pipe(c, p->cus, p->stream);
     if (ce == hipErrorNotSupported) ce = p->ops_col->col(COL_SHRINK, c, p->stream);
-    HIP_TRY(ce);
+    P3D_TRY(ce);
     return P3D_OK;
 }
 
@@ -926,11 +905,11 @@ int shearlet_col_stats_pair(p3d_plan* p, int nb, int nsh, const unsigned* sup, i
     c.out = p->work;
     c.partials = p->partials;
     c.sh = shear_args(nullptr, nullptr, nsh, 0, 0, 0, 1, sup, sup_words, true);
-    HIP_TRY(p->ops_col->col_shear_pair(c, p->stream));
+    P3D_TRY(p->ops_col->col_shear_pair(c, p->stream));
     const int tiles = p->nxl / 8;
     std::vector<float> part((size_t)STATS_PARTIAL * tiles * nb * nsh);
-    HIP_TRY(hipMemcpyAsync(part.data(), p->partials, sizeof(float) * part.size(), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpyAsync(part.data(), p->partials, sizeof(float) * part.size(), hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     for (int bs = 0; bs < nb * nsh; ++bs) {
         float smax = -INFINITY, mx = 0.f, mn = INFINITY;
         double sq = 0.0;
@@ -952,7 +931,7 @@ int shearlet_gather_fwd(p3d_plan* p, const float* psi, c32* out, int nb, int nsh
     r.work = p->work;
     r.out = out;
     r.sh = shear_args(psi, nullptr, nsh, 0, 0, 0, 0, sup, sup_words, pair);
-    HIP_TRY(p->ops_row->row(ROW_GATHER_FWD, r, p->stream));
+    P3D_TRY(p->ops_row->row(ROW_GATHER_FWD, r, p->stream));
     return P3D_OK;
 }
 
@@ -966,7 +945,7 @@ int p3d_fft2_c64_dev(p3d_plan* p, const void* in, void* out, int nslices, int in
 {
     int rc = fft2_enqueue(p, in, out, nslices, inverse);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     return P3D_OK;
 }
 
@@ -975,12 +954,12 @@ int p3d_fft2_c64(p3d_plan* p, const void* in, void* out, int nslices, int invers
     int rc = check_batch(p, nslices);
     if (rc) return rc;
     if (!in || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
     const size_t bytes = sizeof(c32) * p->slice_elems() * nslices;
     if ((rc = ensure_staging(p, sizeof(c32) * p->slice_elems() * p->max_slices))) return rc;
-    HIP_TRY(hipMemcpy(p->st_x, in, bytes, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(p->st_x, in, bytes, hipMemcpyHostToDevice));
     if ((rc = p3d_fft2_c64_dev(p, p->st_x, p->st_out, nslices, inverse))) return rc;
-    HIP_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
@@ -990,20 +969,20 @@ int p3d_pocs_sorted_spectrum(p3d_plan* p, const void* x, int nslices, float* pea
     int rc = check_batch(p, nslices);
     if (rc) return rc;
     if (!x || !peaks) return fail(P3D_ERR_INVALID, "NULL buffer");
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
     const size_t per = p->slice_elems(), bytes = sizeof(c32) * per * nslices;
     if (per > 0xffffffffull) return fail(P3D_ERR_UNSUPPORTED, "%zu samples per slice: the segmented sort indexes a slice with 32 bits", per);
     if ((rc = ensure_staging(p, sizeof(c32) * per * p->max_slices))) return rc;
-    HIP_TRY(hipMemcpyAsync(p->st_x, x, bytes, hipMemcpyDefault, p->stream));   // (x may be a device pointer: ordered with the plan's stream)
+    P3D_TRY(hipMemcpyAsync(p->st_x, x, bytes, hipMemcpyDefault, p->stream));   // (x may be a device pointer: ordered with the plan's stream)
     if ((rc = fft2_enqueue(p, p->st_x, p->st_out, nslices, 0))) return rc;
     float* dpeaks = nullptr;
-    HIP_TRY(hipMalloc((void**)&dpeaks, sizeof(float) * 2 * nslices));
+    P3D_TRY(hipMalloc((void**)&dpeaks, sizeof(float) * 2 * nslices));
     const hipError_t e = lex_sort_desc((c32*)p->st_out, p->st_x, per, nslices, dpeaks, p->stream);   // keys in st_out, sorted in st_x
     hipError_t e2 = hipSuccess;
     if (e == hipSuccess) e2 = hipMemcpy(peaks, dpeaks, sizeof(float) * 2 * nslices, hipMemcpyDeviceToHost);
     hipFree(dpeaks);
-    HIP_TRY(e);
-    HIP_TRY(e2);
+    P3D_TRY(e);
+    P3D_TRY(e2);
     p->sorted_slices = nslices;
     return P3D_OK;
 }
@@ -1014,7 +993,7 @@ int p3d_pocs_data_driven_pick(p3d_plan* p, int nslices, int niter, const float* 
     if (!bounds || !tau || !count || niter < 1) return fail(P3D_ERR_INVALID, "NULL buffer or niter < 1");
     if (p->sorted_slices != nslices || nslices < 1)
         return fail(P3D_ERR_INVALID, "p3d_pocs_sorted_spectrum has not just run on %d slices of this plan", nslices);
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
     float *dbounds = nullptr, *dtau = nullptr;
     long long* dcount = nullptr;
     hipError_t e = hipMalloc((void**)&dbounds, sizeof(float) * 4 * nslices);
@@ -1029,7 +1008,7 @@ int p3d_pocs_data_driven_pick(p3d_plan* p, int nslices, int niter, const float* 
     if (dbounds) hipFree(dbounds);
     if (dtau) hipFree(dtau);
     if (dcount) hipFree(dcount);
-    HIP_TRY(e);
+    P3D_TRY(e);
     return P3D_OK;
 }
 
@@ -1039,32 +1018,32 @@ int p3d_fft2_shrink_c64(p3d_plan* p, const void* in, const double* tau, int op, 
     if (rc) return rc;
     if (!in || !out || !tau) return fail(P3D_ERR_INVALID, "NULL buffer");
     if (op < P3D_OP_HARD || op > P3D_OP_GARROTE) return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented", op);
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
     const size_t bytes = sizeof(c32) * p->slice_elems() * nslices;
     if ((rc = ensure_staging(p, sizeof(c32) * p->slice_elems() * p->max_slices))) return rc;
     if (p->tau_cap < (size_t)nslices) {
         if (p->tau) hipFree(p->tau);
         p->tau = nullptr;
         p->tau_cap = 0;
-        HIP_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * nslices));
+        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * nslices));
         p->tau_cap = nslices;
     }
     std::vector<c32> tau_f(nslices);
     for (int s = 0; s < nslices; ++s) tau_f[s] = tau_for_device(tau[2 * s], tau[2 * s + 1], op == P3D_OP_HARD);
-    HIP_TRY(hipMemcpy(p->tau, tau_f.data(), sizeof(c32) * nslices, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->st_x, in, bytes, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(p->tau, tau_f.data(), sizeof(c32) * nslices, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(p->st_x, in, bytes, hipMemcpyHostToDevice));
     if (p->generic) {
         if ((rc = gen_fft2(p, (const c32*)p->st_x, (c32*)p->st_out, nslices, 0, nullptr))) return rc;
-        HIP_TRY(gen_launch_shrink((c32*)p->st_out, p->tau, 1, 0, op, nslices, p->slice_elems(), nullptr, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-        HIP_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
+        P3D_TRY(gen_launch_shrink((c32*)p->st_out, p->tau, 1, 0, op, nslices, p->slice_elems(), nullptr, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
         return P3D_OK;
     }
     RowArgs r = row_args(p, nslices);
     r.x = p->st_x;
     r.work = p->work;
     r.dtype = P3D_C64;
-    HIP_TRY(first_row_pass(p, r));
+    P3D_TRY(first_row_pass(p, r));
     ColArgs c = col_args(p, nslices);
     c.in = p->work;
     c.out = (c32*)p->st_out;
@@ -1073,9 +1052,9 @@ int p3d_fft2_shrink_c64(p3d_plan* p, const void* in, const double* tau, int op, 
     c.niter = 1;
     c.iter = 0;
     c.op = op;
-    HIP_TRY(p->ops_col->col(COL_FWD, c, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
+    P3D_TRY(p->ops_col->col(COL_FWD, c, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
@@ -1099,7 +1078,7 @@ static hipError_t first_row_pass(p3d_plan* p, const RowArgs& r)
 static int pack_mask(p3d_plan* p, const float* mask, int* nonbinary, unsigned* nobs)
 {
     const bool flex_rows = is_flex(p->ops_row);
-    HIP_TRY(hipMemsetAsync(p->flag, 0, 2 * sizeof(int), p->stream));
+    P3D_TRY(hipMemsetAsync(p->flag, 0, 2 * sizeof(int), p->stream));
     *nonbinary = flex_rows ? 1 : 0;
     *nobs = 0;
     p->mix_binary = false;
@@ -1107,12 +1086,12 @@ static int pack_mask(p3d_plan* p, const float* mask, int* nonbinary, unsigned* n
         // rows on the mixed-radix register engine: their own packed words; the float weights stay with every other flexible row pass
         // (`nonbinary` keeps saying so: the callers hand RowArgs::mask on), p->mix_binary says whether the words may be used beside them
         int odd = 0;
-        HIP_TRY(p3d::mix::pack_mask(p->mix_row, mask, p->nil, p->mbits, p->mbase, p->flag, p->stream));
-        HIP_TRY(hipMemcpyAsync(&odd, p->flag, sizeof(int), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipMemcpyAsync(nobs, p->mbase + (size_t)p->nil * p->mix_row->tpl, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(p3d::mix::pack_mask(p->mix_row, mask, p->nil, p->mbits, p->mbase, p->flag, p->stream));
+        P3D_TRY(hipMemcpyAsync(&odd, p->flag, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+        P3D_TRY(hipMemcpyAsync(nobs, p->mbase + (size_t)p->nil * p->mix_row->tpl, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
         p->mix_binary = odd == 0;
-        HIP_TRY(hipMemsetAsync(p->flag, 0, 2 * sizeof(int), p->stream));
+        P3D_TRY(hipMemsetAsync(p->flag, 0, 2 * sizeof(int), p->stream));
         return P3D_OK;
     }
     if (flex_rows) return P3D_OK;
@@ -1125,10 +1104,10 @@ static int pack_mask(p3d_plan* p, const float* mask, int* nonbinary, unsigned* n
         pack_cbase_kernel<<<(p->nil + 255) / 256, 256, 0, p->stream>>>(p->bits64, p->rowbase, p->cbase, p->nil, tpl);
     }
     if (p->use32) pack_mask32_kernel<<<((p->nil / 2) * 32 + 255) / 256, 256, 0, p->stream>>>(p->bits, p->bits32, p->nil);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(nonbinary, p->flag, sizeof(int), hipMemcpyDeviceToHost, p->stream));
-    if (p->nil <= 4096) HIP_TRY(hipMemcpyAsync(nobs, p->rowbase + p->nil, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipMemcpyAsync(nonbinary, p->flag, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+    if (p->nil <= 4096) P3D_TRY(hipMemcpyAsync(nobs, p->rowbase + p->nil, sizeof(unsigned), hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     return P3D_OK;
 }
 
@@ -1146,7 +1125,7 @@ static int ensure_xc(p3d_plan* p, int nslices, unsigned nobs, int dtype)
         if (p->xc) hipFree(p->xc);
         p->xc = nullptr;
         p->xc_cap = 0;
-        HIP_TRY(hipMalloc(&p->xc, need));
+        P3D_TRY(hipMalloc(&p->xc, need));
         p->xc_cap = need;
     }
     return P3D_OK;
@@ -1158,7 +1137,7 @@ int p3d_pocs_prime_dev(p3d_plan* p, const void* x, int dtype, const float* mask,
     if (rc) return rc;
     if (!x || !mask || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
     if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
     if (p->generic || is_flex(p->ops_row) || is_flex(p->ops_col)) return p3d_pocs_stats_dev(p, x, dtype, nslices, stats);   // nothing to run ahead there
     const RunSwitches sw = read_switches();
     int nonbinary = 0;
@@ -1182,7 +1161,7 @@ int p3d_pocs_prime_dev(p3d_plan* p, const void* x, int dtype, const float* mask,
     r.sums = p->rowsum;
     r.dtype = dtype;
     r.real_2048 = sw.real_2048 ? 1 : 0;
-    HIP_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
+    P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
     // float32 cubes: the row pairs of the real path (half the transforms, half-spectrum work buffer) and the statistics of the whole
     // Hermitian spectrum from its stored half (ColArgs::herm_n2).  A run that takes the real path too (hard operator, POCS / FPOCS)
     // finds its first pass done; any other run starts over with the complex first pass.
@@ -1190,18 +1169,18 @@ int p3d_pocs_prime_dev(p3d_plan* p, const void* x, int dtype, const float* mask,
     if (real) {
         const hipError_t re = p->ops_row->row_real(REAL_FIRST, r, p->pipe_wgs, p->stream);
         if (re == hipErrorNotSupported) real = false;
-        else HIP_TRY(re);
+        else P3D_TRY(re);
     }
     int violation = 0;
     if (real) {   // the row pairs live on the compact samples: a cube with energy at unobserved positions takes the complex path
-        HIP_TRY(hipMemcpyAsync(&violation, p->flag + 1, sizeof(int), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(hipMemcpyAsync(&violation, p->flag + 1, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
         if (violation) {
             real = false;
-            HIP_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
+            P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
         }
     }
-    if (!real) HIP_TRY(first_row_pass(p, r));
+    if (!real) P3D_TRY(first_row_pass(p, r));
     reduce_rows_kernel<<<nslices, 256, 0, p->stream>>>(p->rowsum, p->sum0, p->nil);
     ColArgs c = col_args(p, nslices);
     c.in = p->work;
@@ -1212,8 +1191,8 @@ int p3d_pocs_prime_dev(p3d_plan* p, const void* x, int dtype, const float* mask,
         c.herm_n2 = p->nxl;
         tiles = (c.n2 + p->ops_col->col_tile - 1) / p->ops_col->col_tile;
     }
-    HIP_TRY(p->ops_col->col(COL_STATS, c, p->stream));
-    if (compact && !real) HIP_TRY(hipMemcpyAsync(&violation, p->flag + 1, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(p->ops_col->col(COL_STATS, c, p->stream));
+    if (compact && !real) P3D_TRY(hipMemcpyAsync(&violation, p->flag + 1, sizeof(int), hipMemcpyDeviceToHost, p->stream));
     if ((rc = reduce_partials(p, nslices, stats, tiles))) return rc;   // (synchronises the stream)
     p->primed.valid = true;
     p->primed.x = x; p->primed.mask = mask; p->primed.dtype = dtype; p->primed.nslices = nslices;
@@ -1228,24 +1207,24 @@ int p3d_pocs_stats_dev(p3d_plan* p, const void* x, int dtype, int nslices, doubl
     if (rc) return rc;
     if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
     if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
     if (p->generic) {
-        HIP_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * nslices, p->stream));
-        HIP_TRY(gen_launch_update(p->work, x, dtype, nullptr, nullptr, p->rowsum, 0, 0, 0, 1.0f, nslices, p->slice_elems(), nullptr, 0,
+        P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * nslices, p->stream));
+        P3D_TRY(gen_launch_update(p->work, x, dtype, nullptr, nullptr, p->rowsum, 0, 0, 0, 1.0f, nslices, p->slice_elems(), nullptr, 0,
                                   p->stream));
         if ((rc = gen_fft2(p, p->work, p->work, nslices, 0, nullptr))) return rc;
-        HIP_TRY(gen_launch_stats(p->work, p->partials, nslices, p->slice_elems(), p->tiles, p->stream));
+        P3D_TRY(gen_launch_stats(p->work, p->partials, nslices, p->slice_elems(), p->tiles, p->stream));
         return reduce_partials(p, nslices, stats);
     }
     RowArgs r = row_args(p, nslices);
     r.x = x;
     r.work = p->work;
     r.dtype = dtype;
-    HIP_TRY(first_row_pass(p, r));
+    P3D_TRY(first_row_pass(p, r));
     ColArgs c = col_args(p, nslices);
     c.in = p->work;
     c.partials = p->partials;
-    HIP_TRY(p->ops_col->col(COL_STATS, c, p->stream));
+    P3D_TRY(p->ops_col->col(COL_STATS, c, p->stream));
     return reduce_partials(p, nslices, stats);
 }
 
@@ -1255,10 +1234,10 @@ int p3d_pocs_stats(p3d_plan* p, const void* x, int dtype, int nslices, double* s
     if (rc) return rc;
     if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
     if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
     if ((rc = ensure_staging(p, sizeof(c32) * p->slice_elems() * p->max_slices))) return rc;
     const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
-    HIP_TRY(hipMemcpy(p->st_x, x, esz * p->slice_elems() * nslices, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(p->st_x, x, esz * p->slice_elems() * nslices, hipMemcpyHostToDevice));
     return p3d_pocs_stats_dev(p, p->st_x, dtype, nslices, stats);
 }
 
@@ -1282,7 +1261,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented by the HIP kernels", prm->thresh_op);
     if (prm->version < P3D_VER_REGULAR || prm->version > P3D_VER_ADAPTIVE)
         return fail(P3D_ERR_INVALID, "unknown version %d", prm->version);
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
 
     const int niter = prm->niter;
     const RunSwitches sw = read_switches();
@@ -1296,7 +1275,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         if (p->tau) hipFree(p->tau);
         p->tau = nullptr;
         p->tau_cap = 0;
-        HIP_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * ntau));
+        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * ntau));
         p->tau_cap = ntau;
     }
     const size_t nsum = (size_t)(niter + 1) * nslices;
@@ -1304,7 +1283,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         if (p->sums) hipFree(p->sums);
         p->sums = nullptr;
         p->sums_cap = 0;
-        HIP_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
+        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
         p->sums_cap = nsum;
     }
     std::vector<c32> tau_f(ntau);
@@ -1312,16 +1291,16 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     std::vector<int> done_h(nslices, 0);
     if (active)
         for (int s = 0; s < nslices; ++s) done_h[s] = active[s] ? 0 : -1;
-    HIP_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
 
     size_t nev = 0;
     if (profile) {
         const size_t need = 2 * (size_t)niter + 2;
         while (p->prof_events.size() < need) {
             hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
+            P3D_TRY(hipEventCreate(&e));
             p->prof_events.push_back(e);
         }
     }
@@ -1330,7 +1309,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         return hipEventRecord(p->prof_events[nev++], p->stream);
     };
 
-    HIP_TRY(hipEventRecord(p->ev0, p->stream));
+    P3D_TRY(hipEventRecord(p->ev0, p->stream));
 
     // The -percentile operators rank the moduli of the whole spectrum (np.percentile, POCS.py:43-57).  The fused passes can do it
     // where the column-blocked work buffer holds exactly the slice (no padding columns): the column pass is split into forward
@@ -1352,8 +1331,8 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         bool any_off = early;
         for (int s = 0; s < nslices; ++s) any_off = any_off || done_h[s] != 0;
         const int* done_d = any_off ? p->done : nullptr;
-        HIP_TRY(hipEventRecord(p->ev0, p->stream));
-        HIP_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, nslices, per_slice,
+        P3D_TRY(hipEventRecord(p->ev0, p->stream));
+        P3D_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, nslices, per_slice,
                                   done_d, 0, p->stream));
         for (int k = 0; k < niter; ++k) {
             const bool last = k + 1 == niter;
@@ -1371,35 +1350,35 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
                     sel_h[((size_t)nslices + s) * 8] = (unsigned)std::min(fl + 1.0, (double)(per_slice - 1));
                     frac_h[s] = (float)(pos - fl);
                 }
-                HIP_TRY(hipMemcpyAsync(p->pct_sel, sel_h.data(), sizeof(unsigned) * sel_h.size(), hipMemcpyHostToDevice, p->stream));
-                HIP_TRY(hipMemcpyAsync(p->pct_frac, frac_h.data(), sizeof(float) * nslices, hipMemcpyHostToDevice, p->stream));
-                HIP_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * 2048 * (size_t)nslices, p->stream));
+                P3D_TRY(hipMemcpyAsync(p->pct_sel, sel_h.data(), sizeof(unsigned) * sel_h.size(), hipMemcpyHostToDevice, p->stream));
+                P3D_TRY(hipMemcpyAsync(p->pct_frac, frac_h.data(), sizeof(float) * nslices, hipMemcpyHostToDevice, p->stream));
+                P3D_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * 2048 * (size_t)nslices, p->stream));
                 for (int which = 0; which < 2; ++which) {
                     unsigned* sel = p->pct_sel + (size_t)which * nslices * 8;
                     for (int level = 0; level < 3; ++level) {
-                        HIP_TRY(gen_launch_pct_hist(p->work, per_slice, sel, p->pct_hist, level, nslices, p->stream));
-                        HIP_TRY(gen_launch_pct_scan(sel, p->pct_hist, level, nslices, p->stream));
+                        P3D_TRY(gen_launch_pct_hist(p->work, per_slice, sel, p->pct_hist, level, nslices, p->stream));
+                        P3D_TRY(gen_launch_pct_scan(sel, p->pct_hist, level, nslices, p->stream));
                     }
                 }
-                HIP_TRY(gen_launch_pct_tau(p->pct_sel, p->pct_sel + (size_t)nslices * 8, p->pct_frac, p->tau, niter, k, nslices, p->stream));
-                HIP_TRY(hipStreamSynchronize(p->stream));  // sel_h / frac_h are reused next iteration
+                P3D_TRY(gen_launch_pct_tau(p->pct_sel, p->pct_sel + (size_t)nslices * 8, p->pct_frac, p->tau, niter, k, nslices, p->stream));
+                P3D_TRY(hipStreamSynchronize(p->stream));  // sel_h / frac_h are reused next iteration
             }
-            HIP_TRY(gen_launch_shrink(p->work, p->tau, niter, k, base_op, nslices, per_slice, done_d, p->stream));
+            P3D_TRY(gen_launch_shrink(p->work, p->tau, niter, k, base_op, nslices, per_slice, done_d, p->stream));
             if ((rc = gen_fft2(p, p->work, p->work, nslices, 1, done_d))) return rc;
-            HIP_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0,
+            P3D_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0,
                                       (early || last) ? 1 : 0, (float)prm->alpha, nslices, per_slice, p->done, last ? 1 : 0, p->stream));
             if (early) conv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
         }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(p->ev1, p->stream));
-        HIP_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-        if (sums) HIP_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(hipGetLastError());
+        P3D_TRY(hipEventRecord(p->ev1, p->stream));
+        P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
+        if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
         if (niter_done)
             for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
         if (elapsed_ms) {
             float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+            P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
             *elapsed_ms = ms;
         }
         p->prof_col_n = p->prof_row_n = 0;
@@ -1414,7 +1393,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     if (primed_in) {   // packed by p3d_pocs_prime_dev, still in place
         nonbinary = primed_state.nonbinary;
         nobs = primed_state.nobs;
-        HIP_TRY(hipMemsetAsync(p->flag, 0, 2 * sizeof(int), p->stream));
+        P3D_TRY(hipMemsetAsync(p->flag, 0, 2 * sizeof(int), p->stream));
     } else if ((rc = pack_mask(p, mask, &nonbinary, &nobs))) {
         return rc;
     }
@@ -1430,16 +1409,16 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         ra.tw_row = p->tw_row; ra.tw_col = p->tw_col;
         ra.nslices = nslices; ra.niter = niter; ra.op = base_op; ra.dtype = dtype;
         ra.alpha = (float)prm->alpha; ra.scale = (float)(1.0 / ((double)p->nil * (double)p->nxl)); ra.eps = prm->eps;
-        HIP_TRY(resident_launch(p->nil, p->nxl, ra, p->stream));
-        HIP_TRY(hipEventRecord(p->ev1, p->stream));
-        HIP_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-        if (sums) HIP_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(resident_launch(p->nil, p->nxl, ra, p->stream));
+        P3D_TRY(hipEventRecord(p->ev1, p->stream));
+        P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
+        if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
         if (niter_done)
             for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
         if (elapsed_ms) {
             float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+            P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
             *elapsed_ms = ms;
         }
         p->last_nonzero_fraction = -1.0;
@@ -1484,7 +1463,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     r.alpha = (float)prm->alpha;
     r.sum_row = 0;
     // rows of finished / empty slices are skipped by the kernels: their partial sums must read as zero
-    HIP_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
+    P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
     // Real cubes with the hard operator: the spectrum stays Hermitian, so row pairs share one complex transform and the work
     // buffer holds half the columns (row_real_kernel).  Needs the compact observed samples and the lane-mask tables.
     // (The flexible-length row pass keeps the pair in LDS and takes any real mask: no compact samples, no tables needed there.)
@@ -1495,7 +1474,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     if (real_path && !primed_real) {
         const hipError_t re = p->ops_row->row_real(REAL_FIRST, r, p->pipe_wgs, p->stream);
         if (re == hipErrorNotSupported) real_path = false;
-        else HIP_TRY(re);
+        else P3D_TRY(re);
     }
     // Rows on the mixed-radix register engine (p3d_mix.hpp) with a binary mask: the packed words instead of the float weights, and in the
     // steady state the compact observed samples its first pass writes (thread-major order, RowArgs::mbase) -- 1 bit + 8 (1 - missing) bytes
@@ -1514,23 +1493,23 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     // mix otherwise): work buffer, compact samples and sum |x_obs| are there.
     const bool primed = primed_in && !adaptive && (real_path ? primed_real : !primed_state.real);
     if (primed) {
-        HIP_TRY(hipMemcpyAsync(p->sums, p->sum0, sizeof(double) * nslices, hipMemcpyDeviceToDevice, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->sums, p->sum0, sizeof(double) * nslices, hipMemcpyDeviceToDevice, p->stream));
         // the primed pass knew nothing of `active`: a slice the caller switched off reports sums[0] = 0, as on the unprimed path
         if (any_off) zero_off_sums_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices);
         if (primed_state.violation) r.xc = nullptr;
     } else if (!real_path) {
-        HIP_TRY(first_row_pass(p, r));
+        P3D_TRY(first_row_pass(p, r));
     }
     if ((compact || mix_compact) && !primed) {  // did every unobserved position hold a zero?
         int violation = 0;
-        HIP_TRY(hipMemcpyAsync(&violation, p->flag + 1, sizeof(int), hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(hipMemcpyAsync(&violation, p->flag + 1, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
         if (violation) {
             r.xc = nullptr;
             if (real_path) {   // the row-pair passes live on the compact samples: take the complex path from the start
                 real_path = false;
-                HIP_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
-                HIP_TRY(first_row_pass(p, r));
+                P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
+                P3D_TRY(first_row_pass(p, r));
             }
         }
     }
@@ -1550,7 +1529,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     if (sparse) {
         c.nzflag = p->nzflag;
         r.zero_off = (unsigned)(wk_slice_stride(p->nil, p->nxl) * (size_t)p->max_slices);
-        HIP_TRY(hipMemsetAsync(p->nzcount, 0, sizeof(unsigned long long), p->stream));
+        P3D_TRY(hipMemsetAsync(p->nzcount, 0, sizeof(unsigned long long), p->stream));
     }
     // The persistent column pass (col_pipe_kernel) wins where nearly all tiles end at the threshold (-4 ... -12 % by shape at 4 % kept
     // blocks) and loses as soon as a noticeable share is transformed back and stored (+14 % at the 6 % of a 20-iteration job, +9 % dense:
@@ -1572,9 +1551,9 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     if (percentile) {
         const size_t per_slice = p->slice_elems();
         if (!p->pct_sel) {
-            HIP_TRY(hipMalloc((void**)&p->pct_sel, sizeof(unsigned) * 16 * (size_t)p->max_slices));
-            HIP_TRY(hipMalloc((void**)&p->pct_hist, sizeof(unsigned) * 2048 * (size_t)p->max_slices));
-            HIP_TRY(hipMalloc((void**)&p->pct_frac, sizeof(float) * (size_t)p->max_slices));
+            P3D_TRY(hipMalloc((void**)&p->pct_sel, sizeof(unsigned) * 16 * (size_t)p->max_slices));
+            P3D_TRY(hipMalloc((void**)&p->pct_hist, sizeof(unsigned) * 2048 * (size_t)p->max_slices));
+            P3D_TRY(hipMalloc((void**)&p->pct_frac, sizeof(float) * (size_t)p->max_slices));
         }
         pct_sel_h.assign((size_t)niter * nslices * 16, 0u);
         pct_frac_h.assign((size_t)niter * nslices, 0.f);
@@ -1590,7 +1569,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
                 sel[((size_t)nslices + s) * 8] = (unsigned)std::min(fl + 1.0, (double)(per_slice - 1));
                 pct_frac_h[(size_t)k * nslices + s] = (float)(pos - fl);
             }
-        HIP_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * 2048 * (size_t)nslices, p->stream));
+        P3D_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * 2048 * (size_t)nslices, p->stream));
     }
 
     // The cost sums of the iterations (sum |x| per slice) decide the early exit and fill the caller's table.  A job with neither
@@ -1602,7 +1581,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     // (r.xc is null whenever the first pass wrote none: non-binary mask, no compact samples wanted, energy at unobserved traces)
     const bool fam32 = !real_path && p->use32 && r.xc != nullptr && r.bits32 != nullptr;
     if (no_sums && fam32 && !adaptive) r.sums = nullptr;
-    HIP_TRY(stamp());
+    P3D_TRY(stamp());
     int last_finalized = 0;   // early exit: slices with done <= last_finalized have been handed to `out`
     // Debug mode of the invariant the deferred finalize rests on (RowArgs::only_done_lo, ColArgs::done): the work slice of a converged slice
     // that has not been handed back yet must not change.  One blocking round trip per iteration: tests only (tests/test_gpu_parity.py).
@@ -1610,7 +1589,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     std::vector<unsigned long long> done_sum_first(check_done_rows ? nslices : 0, 0ull), done_sum_now(check_done_rows ? nslices : 0, 0ull);
     std::vector<char> done_sum_seen(check_done_rows ? nslices : 0, 0);
     unsigned long long* done_sum_d = nullptr;
-    if (check_done_rows) HIP_TRY(hipMalloc((void**)&done_sum_d, sizeof(unsigned long long) * nslices));
+    if (check_done_rows) P3D_TRY(hipMalloc((void**)&done_sum_d, sizeof(unsigned long long) * nslices));
     struct FreeSum { unsigned long long* p; ~FreeSum() { if (p) hipFree(p); } } free_sum{done_sum_d};
     for (int k = 0; k < niter; ++k) {
         c.iter = k;
@@ -1620,24 +1599,24 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
             ColArgs cf = c;
             cf.tau = nullptr;
             cf.nzflag = nullptr;
-            HIP_TRY(p->ops_col->col(COL_FWD, cf, p->stream));
-            HIP_TRY(hipMemcpyAsync(p->pct_sel, &pct_sel_h[(size_t)k * nslices * 16], sizeof(unsigned) * 16 * (size_t)nslices, hipMemcpyHostToDevice, p->stream));
-            HIP_TRY(hipMemcpyAsync(p->pct_frac, &pct_frac_h[(size_t)k * nslices], sizeof(float) * nslices, hipMemcpyHostToDevice, p->stream));
+            P3D_TRY(p->ops_col->col(COL_FWD, cf, p->stream));
+            P3D_TRY(hipMemcpyAsync(p->pct_sel, &pct_sel_h[(size_t)k * nslices * 16], sizeof(unsigned) * 16 * (size_t)nslices, hipMemcpyHostToDevice, p->stream));
+            P3D_TRY(hipMemcpyAsync(p->pct_frac, &pct_frac_h[(size_t)k * nslices], sizeof(float) * nslices, hipMemcpyHostToDevice, p->stream));
             for (int which = 0; which < 2; ++which) {
                 unsigned* sel = p->pct_sel + (size_t)which * nslices * 8;
                 for (int level = 0; level < 3; ++level) {
-                    HIP_TRY(gen_launch_pct_hist(p->work, per_slice, sel, p->pct_hist, level, nslices, p->stream));
-                    HIP_TRY(gen_launch_pct_scan(sel, p->pct_hist, level, nslices, p->stream));
+                    P3D_TRY(gen_launch_pct_hist(p->work, per_slice, sel, p->pct_hist, level, nslices, p->stream));
+                    P3D_TRY(gen_launch_pct_scan(sel, p->pct_hist, level, nslices, p->stream));
                 }
             }
-            HIP_TRY(gen_launch_pct_tau(p->pct_sel, p->pct_sel + (size_t)nslices * 8, p->pct_frac, p->tau, niter, k, nslices, p->stream));
-            HIP_TRY(gen_launch_shrink(p->work, p->tau, niter, k, base_op, nslices, per_slice, c.done, p->stream));
-            HIP_TRY(p->ops_col->col(COL_INV, cf, p->stream));
+            P3D_TRY(gen_launch_pct_tau(p->pct_sel, p->pct_sel + (size_t)nslices * 8, p->pct_frac, p->tau, niter, k, nslices, p->stream));
+            P3D_TRY(gen_launch_shrink(p->work, p->tau, niter, k, base_op, nslices, per_slice, c.done, p->stream));
+            P3D_TRY(p->ops_col->col(COL_INV, cf, p->stream));
         } else {
             hipError_t ce = hipErrorNotSupported;
             if (colpipe) ce = p->ops_col->col_pipe(c, p->cus, p->stream);
             if (ce == hipErrorNotSupported) ce = p->ops_col->col(COL_ITER, c, p->stream);
-            HIP_TRY(ce);
+            P3D_TRY(ce);
         }
         if (sparse && real_path && !flex_rows) {
             nz_real_kernel<<<(nslices * 16 * (p->ops_row->tpl >= 64 ? p->ops_row->tpl / 64 : 1) + 3) / 4, 256, 0, p->stream>>>(p->nzflag, p->nzl, p->nzcount, nslices, tiles_work, col_t, p->nxl, p->ops_row->tpl, c.done);
@@ -1654,43 +1633,43 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
             r.nzm = p->nzm;
             r.nzl = p->nzl;
         }
-        HIP_TRY(stamp());
+        P3D_TRY(stamp());
         r.sum_row = k + 1;
         bool piped = false;
         if (real_path) {
-            HIP_TRY(p->ops_row->row_real(k + 1 < niter ? REAL_MID : REAL_LAST, r, p->pipe_wgs, p->stream));
+            P3D_TRY(p->ops_row->row_real(k + 1 < niter ? REAL_MID : REAL_LAST, r, p->pipe_wgs, p->stream));
             piped = true;
         } else if (fam32) {
             const hipError_t fe = p->ops_row->row_pipe32(k + 1 < niter ? PIPE_MID : PIPE_LAST, r, p->pipe_wgs, p->stream);
             if (fe == hipErrorNotSupported) return fail(P3D_ERR_HIP, "row_pipe32_kernel refused a job its first pass had accepted");
-            HIP_TRY(fe);
+            P3D_TRY(fe);
             piped = true;
         } else if (k + 1 < niter && p->pipe_wgs > 0) {  // steady state: persistent, software-pipelined row pass
             const hipError_t pe = p->ops_row->row_pipe(r, p->pipe_wgs, p->stream);
             if (pe == hipSuccess) piped = true;
-            else if (pe != hipErrorNotSupported) HIP_TRY(pe);
+            else if (pe != hipErrorNotSupported) P3D_TRY(pe);
         }
         if (!piped && k + 1 == niter && p->pipe_wgs > 0 && p->bits64 != nullptr && p->ops_row->row_pipe64 != nullptr) {
             const hipError_t le = p->ops_row->row_pipe64(PIPE_LAST, r, p->pipe_wgs, p->stream);   // last pass: compact samples in, whole rows out
             if (le == hipSuccess) piped = true;
-            else if (le != hipErrorNotSupported) HIP_TRY(le);
+            else if (le != hipErrorNotSupported) P3D_TRY(le);
         }
-        if (!piped) HIP_TRY(p->ops_row->row(k + 1 < niter ? ROW_MID : ROW_LAST, r, p->stream));
-        HIP_TRY(stamp());
+        if (!piped) P3D_TRY(p->ops_row->row(k + 1 < niter ? ROW_MID : ROW_LAST, r, p->stream));
+        P3D_TRY(stamp());
         if (!no_sums) reduce_rows_kernel<<<nslices, 256, 0, p->stream>>>(p->rowsum, p->sums + (size_t)(k + 1) * nslices, p->nil);
         if (early) {
             conv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
             // slices that just finished are skipped from now on: their rows must read as zero afterwards
-            HIP_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
+            P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * (size_t)p->nil * nslices, p->stream));
             // (the finalize launch -- mostly workgroups that find nothing to do -- runs every FIN_EVERY iterations and before the last pass: a slice that has
             // converged keeps its work rows, nothing touches them any more)
             constexpr int FIN_EVERY = 8;
             if (check_done_rows) {
                 done_rows_checksum_kernel<<<nslices, 256, 0, p->stream>>>(reinterpret_cast<const unsigned long long*>(p->work), wk_slice_stride(p->nil, n2_work),
                                                                          p->done, last_finalized, done_sum_d);
-                HIP_TRY(hipMemcpyAsync(done_sum_now.data(), done_sum_d, sizeof(unsigned long long) * nslices, hipMemcpyDeviceToHost, p->stream));
-                HIP_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-                HIP_TRY(hipStreamSynchronize(p->stream));
+                P3D_TRY(hipMemcpyAsync(done_sum_now.data(), done_sum_d, sizeof(unsigned long long) * nslices, hipMemcpyDeviceToHost, p->stream));
+                P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
+                P3D_TRY(hipStreamSynchronize(p->stream));
                 for (int s = 0; s < nslices; ++s) {
                     if (done_h[s] <= last_finalized) continue;   // running, empty or already handed back
                     if (!done_sum_seen[s]) { done_sum_seen[s] = 1; done_sum_first[s] = done_sum_now[s]; }
@@ -1711,26 +1690,26 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
                 f.sums = nullptr;
                 f.done = p->done;
                 f.scale = (float)(1.0 / (double)p->nxl);   // one row transform to undo, not a 2-D one
-                if (real_path) HIP_TRY(p->ops_row->row_real(REAL_LAST, f, p->pipe_wgs, p->stream));
-                else HIP_TRY(p->ops_row->row(ROW_LAST, f, p->stream));
+                if (real_path) P3D_TRY(p->ops_row->row_real(REAL_LAST, f, p->pipe_wgs, p->stream));
+                else P3D_TRY(p->ops_row->row(ROW_LAST, f, p->stream));
             }
         }
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(p->ev1, p->stream));
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipEventRecord(p->ev1, p->stream));
 
-    HIP_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) HIP_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
+    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
     unsigned long long kept_blocks = 0;
-    if (sparse) HIP_TRY(hipMemcpyAsync(&kept_blocks, p->nzcount, sizeof kept_blocks, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (sparse) P3D_TRY(hipMemcpyAsync(&kept_blocks, p->nzcount, sizeof kept_blocks, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     if (sparse) p->last_nonzero_fraction = (double)kept_blocks / ((double)niter * nslices * (real_path ? (n2_work + 7) / 8 : nblocks));
 
     if (niter_done)
         for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
     if (elapsed_ms) {
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
         *elapsed_ms = ms;
     }
     if (profile) {
@@ -1738,8 +1717,8 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         p->prof_col_n = p->prof_row_n = 0;
         for (int k = 0; k < niter; ++k) {
             float a = 0.f, b = 0.f;
-            HIP_TRY(hipEventElapsedTime(&a, p->prof_events[2 * k], p->prof_events[2 * k + 1]));
-            HIP_TRY(hipEventElapsedTime(&b, p->prof_events[2 * k + 1], p->prof_events[2 * k + 2]));
+            P3D_TRY(hipEventElapsedTime(&a, p->prof_events[2 * k], p->prof_events[2 * k + 1]));
+            P3D_TRY(hipEventElapsedTime(&b, p->prof_events[2 * k + 1], p->prof_events[2 * k + 2]));
             p->prof_col_ms += a;
             p->prof_col_n += 1;
             if (k + 1 < niter) {  // the last space pass is ROW_LAST (no forward transform): not averaged in
@@ -1759,36 +1738,25 @@ int p3d_pocs_run(p3d_plan* p, const void* x, int dtype, const float* mask, const
     if (rc) return rc;
     if (!x || !mask || !out) return fail(P3D_ERR_INVALID, "NULL argument");
     if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    HIP_TRY(hipSetDevice(p->device));
+    P3D_TRY(hipSetDevice(p->device));
     if ((rc = ensure_staging(p, sizeof(c32) * p->slice_elems() * p->max_slices))) return rc;
     const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
     const size_t bytes = esz * p->slice_elems() * nslices;
-    HIP_TRY(hipMemcpy(p->st_x, x, bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->st_mask, mask, sizeof(float) * p->slice_elems(), hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(p->st_x, x, bytes, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(p->st_mask, mask, sizeof(float) * p->slice_elems(), hipMemcpyHostToDevice));
     if ((rc = p3d_pocs_run_dev(p, p->st_x, dtype, p->st_mask, tau, active, prm, p->st_out, nslices, niter_done, sums,
                                elapsed_ms)))
         return rc;
-    HIP_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
-
-namespace {
-struct DevBuf {  // frees on scope exit
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
-}  // namespace
 
 static int helper_check(int device, size_t ntraces, int nfft)
 {
     if (ntraces < 1 || nfft < 1) return fail(P3D_ERR_INVALID, "ntraces and nfft must be positive");
     if (nfft > GEN_MAX_N || gen_make_plan(nfft).nf < 0) return fail(P3D_ERR_UNSUPPORTED, "nfft = %d: lengths up to %d are supported", nfft, GEN_MAX_N);
     if (ntraces > 2147483647u) return fail(P3D_ERR_INVALID, "too many traces for one call: split the cube");
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    HIP_TRY(hipSetDevice(device));
-    return P3D_OK;
+    return use_device(device);
 }
 
 static double fft_freq(int k, int nfft, double dt) { return (k < (nfft + 1) / 2 ? k : k - nfft) / (nfft * dt); }  // np.fft.fftfreq
@@ -1804,10 +1772,10 @@ static int axis0_fft_impl(int device, c32* work, int nfft, size_t ntr, int inver
         std::vector<c32> tw(nfft);
         gen_build_twiddles(nfft, tw.data());
         DevBuf dtw;
-        HIP_TRY(hipMalloc(&dtw.p, sizeof(c32) * nfft));
-        HIP_TRY(hipMemcpy(dtw.p, tw.data(), sizeof(c32) * nfft, hipMemcpyHostToDevice));
-        HIP_TRY(gen_launch_line_fft(work, work, (const c32*)dtw.p, pl, inverse ? INV : FWD, 1.0f, 1, nfft, (int)ntr, false, nullptr, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
+        P3D_TRY(hipMalloc(&dtw.p, sizeof(c32) * nfft));
+        P3D_TRY(hipMemcpy(dtw.p, tw.data(), sizeof(c32) * nfft, hipMemcpyHostToDevice));
+        P3D_TRY(gen_launch_line_fft(work, work, (const c32*)dtw.p, pl, inverse ? INV : FWD, 1.0f, 1, nfft, (int)ntr, false, nullptr, nullptr));
+        P3D_TRY(hipDeviceSynchronize());
         return P3D_OK;
     }
     std::vector<c32> host;
@@ -1818,8 +1786,8 @@ static int axis0_fft_impl(int device, c32* work, int nfft, size_t ntr, int inver
         ops->build_col_tw(host.data());
     }
     DevBuf dtw;
-    HIP_TRY(hipMalloc(&dtw.p, sizeof(c32) * host.size()));
-    HIP_TRY(hipMemcpy(dtw.p, host.data(), sizeof(c32) * host.size(), hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dtw.p, sizeof(c32) * host.size()));
+    P3D_TRY(hipMemcpy(dtw.p, host.data(), sizeof(c32) * host.size(), hipMemcpyHostToDevice));
     ColArgs c{};
     c.tw = (const c32*)dtw.p;
     c.in = work;
@@ -1828,9 +1796,9 @@ static int axis0_fft_impl(int device, c32* work, int nfft, size_t ntr, int inver
     c.nslices = 1;
     c.len = nfft;
     c.in_std = c.out_std = 1;
-    HIP_TRY(hipDeviceGetAttribute(&c.cus, hipDeviceAttributeMultiprocessorCount, device));   // (no plan here: the device the caller named)
-    HIP_TRY(ops->col(inverse ? COL_INV : COL_FWD, c, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceGetAttribute(&c.cus, hipDeviceAttributeMultiprocessorCount, device));   // (no plan here: the device the caller named)
+    P3D_TRY(ops->col(inverse ? COL_INV : COL_FWD, c, nullptr));
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
@@ -1850,14 +1818,14 @@ int p3d_time2freq_dev(int device, const float* x, int nt, size_t ntr, double dt,
         fac[k] = c32{(float)(dt * w * std::cos(ang)), (float)(dt * w * std::sin(ang))};
     }
     DevBuf dwork, dfac;
-    HIP_TRY(hipMalloc(&dwork.p, sizeof(c32) * (size_t)nfft * ntr));
-    HIP_TRY(hipMalloc(&dfac.p, sizeof(c32) * nfreq));
-    HIP_TRY(hipMemcpy(dfac.p, fac.data(), sizeof(c32) * nfreq, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dwork.p, sizeof(c32) * (size_t)nfft * ntr));
+    P3D_TRY(hipMalloc(&dfac.p, sizeof(c32) * nfreq));
+    P3D_TRY(hipMemcpy(dfac.p, fac.data(), sizeof(c32) * nfreq, hipMemcpyHostToDevice));
     c32* work = (c32*)dwork.p;
-    HIP_TRY(gen_launch_t2f_pad(x, work, nt, nfft, ntr, nullptr));
+    P3D_TRY(gen_launch_t2f_pad(x, work, nt, nfft, ntr, nullptr));
     if ((rc = axis0_fft_impl(device, work, nfft, ntr, 0))) return rc;
-    HIP_TRY(gen_launch_scale_rows(work, (c32*)out, (const c32*)dfac.p, nfreq, ntr, nullptr));
-    HIP_TRY(hipDeviceSynchronize());
+    P3D_TRY(gen_launch_scale_rows(work, (c32*)out, (const c32*)dfac.p, nfreq, ntr, nullptr));
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
@@ -1870,11 +1838,11 @@ int p3d_time2freq(int device, const float* x, int nt, size_t ntr, double dt, dou
     if (rc) return rc;
     const int nfreq = real_only ? nfft / 2 + 1 : nfft;
     DevBuf dx, dout;
-    HIP_TRY(hipMalloc(&dx.p, sizeof(float) * (size_t)nt * ntr));
-    HIP_TRY(hipMalloc(&dout.p, sizeof(c32) * (size_t)nfreq * ntr));
-    HIP_TRY(hipMemcpy(dx.p, x, sizeof(float) * (size_t)nt * ntr, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dx.p, sizeof(float) * (size_t)nt * ntr));
+    P3D_TRY(hipMalloc(&dout.p, sizeof(c32) * (size_t)nfreq * ntr));
+    P3D_TRY(hipMemcpy(dx.p, x, sizeof(float) * (size_t)nt * ntr, hipMemcpyHostToDevice));
     if ((rc = p3d_time2freq_dev(device, (const float*)dx.p, nt, ntr, dt, t0, nfft, real_only, window, dout.p))) return rc;
-    HIP_TRY(hipMemcpy(out, dout.p, sizeof(c32) * (size_t)nfreq * ntr, hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(out, dout.p, sizeof(c32) * (size_t)nfreq * ntr, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
@@ -1901,17 +1869,17 @@ int p3d_freq2time_dev(int device, const void* X, int nfreq, const int32_t* kidx,
         fac[k] = c32{(float)std::cos(ang), (float)std::sin(ang)};
     }
     DevBuf dwork, dfac, dsrc;
-    HIP_TRY(hipMalloc(&dwork.p, sizeof(c32) * (size_t)nfft * ntr));
-    HIP_TRY(hipMalloc(&dfac.p, sizeof(c32) * nfft));
-    HIP_TRY(hipMalloc(&dsrc.p, sizeof(int) * nfft));
-    HIP_TRY(hipMemcpy(dfac.p, fac.data(), sizeof(c32) * nfft, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dsrc.p, src.data(), sizeof(int) * nfft, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dwork.p, sizeof(c32) * (size_t)nfft * ntr));
+    P3D_TRY(hipMalloc(&dfac.p, sizeof(c32) * nfft));
+    P3D_TRY(hipMalloc(&dsrc.p, sizeof(int) * nfft));
+    P3D_TRY(hipMemcpy(dfac.p, fac.data(), sizeof(c32) * nfft, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(dsrc.p, src.data(), sizeof(int) * nfft, hipMemcpyHostToDevice));
     c32* work = (c32*)dwork.p;
-    HIP_TRY(gen_launch_f2t_fill((const c32*)X, work, (const c32*)dfac.p, (const int*)dsrc.p, nfft, ntr, nullptr));
+    P3D_TRY(gen_launch_f2t_fill((const c32*)X, work, (const c32*)dfac.p, (const int*)dsrc.p, nfft, ntr, nullptr));
     if ((rc = axis0_fft_impl(device, work, nfft, ntr, 1))) return rc;
     // true_amplitude: the inverse carries 1/(nfft*dt)
-    HIP_TRY(gen_launch_real_part(work, out, (size_t)nfft * ntr, (float)(1.0 / (nfft * dt)), nullptr));
-    HIP_TRY(hipDeviceSynchronize());
+    P3D_TRY(gen_launch_real_part(work, out, (size_t)nfft * ntr, (float)(1.0 / (nfft * dt)), nullptr));
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
@@ -1923,11 +1891,11 @@ int p3d_freq2time(int device, const void* X, int nfreq, const int32_t* kidx, siz
     int rc = helper_check(device, ntr, nfft);
     if (rc) return rc;
     DevBuf dX, dout;
-    HIP_TRY(hipMalloc(&dX.p, sizeof(c32) * (size_t)nfreq * ntr));
-    HIP_TRY(hipMalloc(&dout.p, sizeof(float) * (size_t)nfft * ntr));
-    HIP_TRY(hipMemcpy(dX.p, X, sizeof(c32) * (size_t)nfreq * ntr, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dX.p, sizeof(c32) * (size_t)nfreq * ntr));
+    P3D_TRY(hipMalloc(&dout.p, sizeof(float) * (size_t)nfft * ntr));
+    P3D_TRY(hipMemcpy(dX.p, X, sizeof(c32) * (size_t)nfreq * ntr, hipMemcpyHostToDevice));
     if ((rc = p3d_freq2time_dev(device, dX.p, nfreq, kidx, ntr, dt, t0, nfft, real_only, (float*)dout.p))) return rc;
-    HIP_TRY(hipMemcpy(out, dout.p, sizeof(float) * (size_t)nfft * ntr, hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(out, dout.p, sizeof(float) * (size_t)nfft * ntr, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 

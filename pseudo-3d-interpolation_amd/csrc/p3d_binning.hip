@@ -21,36 +21,17 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <vector>
 
 #include "p3d.h"
-#include "p3d_internal.hpp"
+#include "p3d_host.hpp"
 #include "p3d_sortnet.hpp"
 
+using p3d::DevBuf;
+using p3d::fail;
+using p3d::use_device;
+
 namespace {
-
-int bfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define B_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return bfail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
 
 enum { BIN_AVERAGE = 0, BIN_MEDIAN = 1, BIN_NEAREST = 2, BIN_IDW = 3 };
 
@@ -235,30 +216,21 @@ int launch(const BinArgs& a0, int method, hipStream_t stream)
     a.ntiles_t = (unsigned)((a.nt + TS - 1) / TS);
     const unsigned long long blocks = (unsigned long long)a.ntiles_x * (unsigned long long)a.nil * a.ntiles_t;
     if (blocks == 0) return P3D_OK;
-    if (blocks > 0x7fffffffull) return bfail(P3D_ERR_UNSUPPORTED, "cube of %lld x %lld x %lld needs %llu workgroups", a.nt, a.nil, a.nxl, blocks);
+    if (blocks > 0x7fffffffull) return fail(P3D_ERR_UNSUPPORTED, "cube of %lld x %lld x %lld needs %llu workgroups", a.nt, a.nil, a.nxl, blocks);
     switch (method) {
     case BIN_AVERAGE: bin_stack_kernel<BIN_AVERAGE><<<(unsigned)blocks, 256, 0, stream>>>(a); break;
     case BIN_MEDIAN: bin_stack_kernel<BIN_MEDIAN><<<(unsigned)blocks, 256, 0, stream>>>(a); break;
     case BIN_NEAREST: bin_stack_kernel<BIN_NEAREST><<<(unsigned)blocks, 256, 0, stream>>>(a); break;
     default: bin_stack_kernel<BIN_IDW><<<(unsigned)blocks, 256, 0, stream>>>(a); break;
     }
-    B_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
 int check_common(int nt, int nil, int nxl, int method)
 {
-    if (nt < 1 || nil < 1 || nxl < 1) return bfail(P3D_ERR_INVALID, "bad cube shape (nt %d, nil %d, nxl %d)", nt, nil, nxl);
-    if (method < BIN_AVERAGE || method > BIN_IDW) return bfail(P3D_ERR_INVALID, "unknown stacking method %d", method);
-    return P3D_OK;
-}
-
-int set_device(int device)
-{
-    int ndev = 0;
-    B_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return bfail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    B_TRY(hipSetDevice(device));
+    if (nt < 1 || nil < 1 || nxl < 1) return fail(P3D_ERR_INVALID, "bad cube shape (nt %d, nil %d, nxl %d)", nt, nil, nxl);
+    if (method < BIN_AVERAGE || method > BIN_IDW) return fail(P3D_ERR_INVALID, "unknown stacking method %d", method);
     return P3D_OK;
 }
 
@@ -269,19 +241,19 @@ extern "C" {
 int p3d_bin_stack(int device, const float* samples, const long long* trace_off, const int* trace_len, const int* shift, const double* weight,
                   size_t ntraces, const long long* bin_start, int nil, int nxl, int nt, int method, size_t max_bytes, float* out)
 {
-    if (!out || !bin_start || (ntraces > 0 && (!samples || !trace_off || !trace_len || !shift))) return bfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!out || !bin_start || (ntraces > 0 && (!samples || !trace_off || !trace_len || !shift))) return fail(P3D_ERR_INVALID, "NULL buffer");
     if (int rc = check_common(nt, nil, nxl, method)) return rc;
-    if (method == BIN_IDW && ntraces > 0 && !weight) return bfail(P3D_ERR_INVALID, "IDW needs weights");
+    if (method == BIN_IDW && ntraces > 0 && !weight) return fail(P3D_ERR_INVALID, "IDW needs weights");
     const long long nbins = (long long)nil * nxl;
-    if (bin_start[0] != 0 || bin_start[nbins] != (long long)ntraces) return bfail(P3D_ERR_INVALID, "bin_start must run from 0 to ntraces");
+    if (bin_start[0] != 0 || bin_start[nbins] != (long long)ntraces) return fail(P3D_ERR_INVALID, "bin_start must run from 0 to ntraces");
     for (long long b = 0; b < nbins; ++b)
-        if (bin_start[b + 1] < bin_start[b]) return bfail(P3D_ERR_INVALID, "bin_start decreases at bin %lld", b);
+        if (bin_start[b + 1] < bin_start[b]) return fail(P3D_ERR_INVALID, "bin_start decreases at bin %lld", b);
     for (size_t t = 0; t < ntraces; ++t)
-        if (trace_len[t] < 0 || trace_off[t] < 0) return bfail(P3D_ERR_INVALID, "trace %zu: negative offset or length", t);
-    if (int rc = set_device(device)) return rc;
+        if (trace_len[t] < 0 || trace_off[t] < 0) return fail(P3D_ERR_INVALID, "trace %zu: negative offset or length", t);
+    if (int rc = use_device(device)) return rc;
 
     size_t free_b = 0, total_b = 0;
-    B_TRY(hipMemGetInfo(&free_b, &total_b));
+    P3D_TRY(hipMemGetInfo(&free_b, &total_b));
     size_t cap = free_b / 2;
     if (max_bytes > 0 && max_bytes < cap) cap = max_bytes;
 
@@ -312,7 +284,7 @@ int p3d_bin_stack(int device, const float* samples, const long long* trace_off, 
     while (cuts.back() < nil) {
         const long long i0 = cuts.back();
         if (bytes_of(i0, i0 + 1) > cap)
-            return bfail(P3D_ERR_UNSUPPORTED, "inline %lld needs %zu device bytes, more than the %zu available", i0, bytes_of(i0, i0 + 1), cap);
+            return fail(P3D_ERR_UNSUPPORTED, "inline %lld needs %zu device bytes, more than the %zu available", i0, bytes_of(i0, i0 + 1), cap);
         long long lo = i0 + 1, hi = nil;                    // largest i1 in [lo, hi] with bytes_of(i0, i1) <= cap (monotone in i1)
         while (lo < hi) {
             const long long mid = lo + (hi - lo + 1) / 2;
@@ -333,14 +305,14 @@ int p3d_bin_stack(int device, const float* samples, const long long* trace_off, 
         max_bins = std::max(max_bins, n * nxl + 1);
     }
     DevBuf dcube, dsmp, doff, dlen, dsh, dw, dbs;
-    B_TRY(hipMalloc(&dcube.p, max_cube * sizeof(float)));
-    B_TRY(hipMalloc(&dbs.p, max_bins * sizeof(long long)));
+    P3D_TRY(hipMalloc(&dcube.p, max_cube * sizeof(float)));
+    P3D_TRY(hipMalloc(&dbs.p, max_bins * sizeof(long long)));
     if (max_tr > 0) {
-        B_TRY(hipMalloc(&dsmp.p, std::max<size_t>(max_span, 1) * sizeof(float)));
-        B_TRY(hipMalloc(&doff.p, max_tr * sizeof(long long)));
-        B_TRY(hipMalloc(&dlen.p, max_tr * sizeof(int)));
-        B_TRY(hipMalloc(&dsh.p, max_tr * sizeof(int)));
-        if (weight) B_TRY(hipMalloc(&dw.p, max_tr * sizeof(double)));
+        P3D_TRY(hipMalloc(&dsmp.p, std::max<size_t>(max_span, 1) * sizeof(float)));
+        P3D_TRY(hipMalloc(&doff.p, max_tr * sizeof(long long)));
+        P3D_TRY(hipMalloc(&dlen.p, max_tr * sizeof(int)));
+        P3D_TRY(hipMalloc(&dsh.p, max_tr * sizeof(int)));
+        if (weight) P3D_TRY(hipMalloc(&dw.p, max_tr * sizeof(double)));
     }
 
     const size_t row = (size_t)nil * nxl * sizeof(float);
@@ -349,35 +321,35 @@ int p3d_bin_stack(int device, const float* samples, const long long* trace_off, 
         long long s0, s1;
         span_of(i0, i1, s0, s1);
         const long long tb = bin_start[i0 * nxl], ntr = bin_start[i1 * nxl] - tb;
-        B_TRY(hipMemcpy(dbs.p, bin_start + i0 * nxl, (size_t)(n * nxl + 1) * sizeof(long long), hipMemcpyHostToDevice));
+        P3D_TRY(hipMemcpy(dbs.p, bin_start + i0 * nxl, (size_t)(n * nxl + 1) * sizeof(long long), hipMemcpyHostToDevice));
         if (ntr > 0) {
-            if (s1 > s0) B_TRY(hipMemcpy(dsmp.p, samples + s0, (size_t)(s1 - s0) * sizeof(float), hipMemcpyHostToDevice));
-            B_TRY(hipMemcpy(doff.p, trace_off + tb, (size_t)ntr * sizeof(long long), hipMemcpyHostToDevice));
-            B_TRY(hipMemcpy(dlen.p, trace_len + tb, (size_t)ntr * sizeof(int), hipMemcpyHostToDevice));
-            B_TRY(hipMemcpy(dsh.p, shift + tb, (size_t)ntr * sizeof(int), hipMemcpyHostToDevice));
-            if (weight) B_TRY(hipMemcpy(dw.p, weight + tb, (size_t)ntr * sizeof(double), hipMemcpyHostToDevice));
+            if (s1 > s0) P3D_TRY(hipMemcpy(dsmp.p, samples + s0, (size_t)(s1 - s0) * sizeof(float), hipMemcpyHostToDevice));
+            P3D_TRY(hipMemcpy(doff.p, trace_off + tb, (size_t)ntr * sizeof(long long), hipMemcpyHostToDevice));
+            P3D_TRY(hipMemcpy(dlen.p, trace_len + tb, (size_t)ntr * sizeof(int), hipMemcpyHostToDevice));
+            P3D_TRY(hipMemcpy(dsh.p, shift + tb, (size_t)ntr * sizeof(int), hipMemcpyHostToDevice));
+            if (weight) P3D_TRY(hipMemcpy(dw.p, weight + tb, (size_t)ntr * sizeof(double), hipMemcpyHostToDevice));
         }
         // offsets of zero-length traces may lie outside the span: they are never dereferenced (tap() checks the length first)
         BinArgs a{(const float*)dsmp.p, (const long long*)doff.p, (const int*)dlen.p, (const int*)dsh.p, (const double*)dw.p,
                   (const long long*)dbs.p, tb, s0, nt, nxl, n, 0, (float*)dcube.p, 0, 0};
         if (int rc = launch(a, method, 0)) return rc;
         const size_t w = (size_t)n * nxl * sizeof(float);
-        B_TRY(hipMemcpy2D(out + (size_t)i0 * nxl, row, dcube.p, w, w, (size_t)nt, hipMemcpyDeviceToHost));
+        P3D_TRY(hipMemcpy2D(out + (size_t)i0 * nxl, row, dcube.p, w, w, (size_t)nt, hipMemcpyDeviceToHost));
     }
-    B_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_bin_stack_dev(int device, const float* samples_dev, const long long* trace_off_dev, const int* trace_len_dev, const int* shift_dev,
                       const double* weight_dev, const long long* bin_start_dev, int nil, int nxl, int nt, int method, float* out_dev)
 {
-    if (!out_dev || !bin_start_dev) return bfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!out_dev || !bin_start_dev) return fail(P3D_ERR_INVALID, "NULL buffer");
     if (int rc = check_common(nt, nil, nxl, method)) return rc;
-    if (method == BIN_IDW && !weight_dev) return bfail(P3D_ERR_INVALID, "IDW needs weights");
-    if (int rc = set_device(device)) return rc;
+    if (method == BIN_IDW && !weight_dev) return fail(P3D_ERR_INVALID, "IDW needs weights");
+    if (int rc = use_device(device)) return rc;
     BinArgs a{samples_dev, trace_off_dev, trace_len_dev, shift_dev, weight_dev, bin_start_dev, 0, 0, nt, nxl, nil, 0, out_dev, 0, 0};
     if (int rc = launch(a, method, 0)) return rc;
-    B_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 

@@ -18,36 +18,17 @@
 
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <vector>
 
 #include "p3d.h"
-#include "p3d_internal.hpp"
+#include "p3d_host.hpp"
 #include "p3d_sortnet.hpp"
 
+using p3d::DevBuf;
+using p3d::fail;
+using p3d::use_device;
+
 namespace {
-
-int dfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define D_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return dfail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
 
 enum { DSP_MEAN = 0, DSP_MEDIAN = 1, DSP_RMS = 2 };
 enum { OUT_SCALED = 0, OUT_MODE = 1, OUT_THRESHOLD = 2, OUT_ZEROS = 3, OUT_MEDIAN = 4 };
@@ -289,21 +270,12 @@ __global__ void __launch_bounds__(BS) despike_replace_kernel(float* __restrict__
     }
 }
 
-int set_device(int device)
-{
-    int ndev = 0;
-    D_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return dfail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    D_TRY(hipSetDevice(device));
-    return P3D_OK;
-}
-
 int check_window(int ntr, int ns, int w, int mode)
 {
-    if (ntr < 1 || ns < 1) return dfail(P3D_ERR_INVALID, "bad section shape (%d traces, %d samples)", ntr, ns);
-    if (mode < DSP_MEAN || mode > DSP_RMS) return dfail(P3D_ERR_INVALID, "unknown amplitude mode %d", mode);
-    if (w < 3 || w % 2 == 0) return dfail(P3D_ERR_INVALID, "the trace window must be an odd number of at least 3 traces, got %d", w);
-    if (w > MAXW) return dfail(P3D_ERR_UNSUPPORTED, "trace windows of up to %d traces are supported, got %d", MAXW, w);
+    if (ntr < 1 || ns < 1) return fail(P3D_ERR_INVALID, "bad section shape (%d traces, %d samples)", ntr, ns);
+    if (mode < DSP_MEAN || mode > DSP_RMS) return fail(P3D_ERR_INVALID, "unknown amplitude mode %d", mode);
+    if (w < 3 || w % 2 == 0) return fail(P3D_ERR_INVALID, "the trace window must be an odd number of at least 3 traces, got %d", w);
+    if (w > MAXW) return fail(P3D_ERR_UNSUPPORTED, "trace windows of up to %d traces are supported, got %d", MAXW, w);
     return P3D_OK;
 }
 
@@ -323,73 +295,73 @@ int detect_dev(const float* section_dev, int ntr, int ns, int w, int mode, float
                unsigned long long* mask_dev, int* counts_dev)
 {
     if (int rc = check_window(ntr, ns, w, mode)) return rc;
-    if (!section_dev || !mask_dev || !counts_dev) return dfail(P3D_ERR_INVALID, "NULL buffer");
-    if (main_end < 0 || main_end > ns || add_start < 0) return dfail(P3D_ERR_INVALID, "view rows outside the section (main_end %d, add_start %d)", main_end, add_start);
+    if (!section_dev || !mask_dev || !counts_dev) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (main_end < 0 || main_end > ns || add_start < 0) return fail(P3D_ERR_INVALID, "view rows outside the section (main_end %d, add_start %d)", main_end, add_start);
     const int one[2] = {0, ntr};
     if (!splits || nsplits < 1) {
         splits = one;
         nsplits = 1;
     }
-    if (splits[0] != 0 || splits[nsplits] != ntr) return dfail(P3D_ERR_INVALID, "split boundaries must run from 0 to the number of traces");
+    if (splits[0] != 0 || splits[nsplits] != ntr) return fail(P3D_ERR_INVALID, "split boundaries must run from 0 to the number of traces");
     std::vector<Tile> tiles;
     for (int s = 0; s < nsplits; ++s) {
-        if (splits[s + 1] <= splits[s]) return dfail(P3D_ERR_INVALID, "split boundaries must ascend");
+        if (splits[s + 1] <= splits[s]) return fail(P3D_ERR_INVALID, "split boundaries must ascend");
         for (int x0 = splits[s]; x0 < splits[s + 1]; x0 += TT) tiles.push_back(Tile{splits[s], splits[s + 1], x0, std::min(x0 + TT, splits[s + 1])});
     }
     const unsigned nsb = (unsigned)((ns + BS - 1) / BS);
     const unsigned long long blocks = (unsigned long long)tiles.size() * nsb;
-    if (blocks > 0x7fffffffull) return dfail(P3D_ERR_UNSUPPORTED, "section too large for one launch (%llu workgroups)", blocks);
+    if (blocks > 0x7fffffffull) return fail(P3D_ERR_UNSUPPORTED, "section too large for one launch (%llu workgroups)", blocks);
     const int nw64 = (ns + 63) / 64;
     DevBuf dt;
-    D_TRY(hipMalloc(&dt.p, tiles.size() * sizeof(Tile)));
-    D_TRY(hipMemcpy(dt.p, tiles.data(), tiles.size() * sizeof(Tile), hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dt.p, tiles.size() * sizeof(Tile)));
+    P3D_TRY(hipMemcpy(dt.p, tiles.data(), tiles.size() * sizeof(Tile), hipMemcpyHostToDevice));
     const Tile* tp = (const Tile*)dt.p;
     const unsigned nb = (unsigned)blocks;
 #define DSP_CASE(W) case W: launch_detect_w<W>(mode, nb, 0, section_dev, tp, nsb, ns, thr, main_end, add_start, mask_dev, nw64); break;
     switch (w) {
         DSP_CASE(3) DSP_CASE(5) DSP_CASE(7) DSP_CASE(9) DSP_CASE(11) DSP_CASE(13) DSP_CASE(15) DSP_CASE(17) DSP_CASE(19) DSP_CASE(21) DSP_CASE(23)
         DSP_CASE(25) DSP_CASE(27) DSP_CASE(29) DSP_CASE(31)
-    default: return dfail(P3D_ERR_UNSUPPORTED, "no kernel for a window of %d traces", w);
+    default: return fail(P3D_ERR_UNSUPPORTED, "no kernel for a window of %d traces", w);
     }
 #undef DSP_CASE
-    D_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     despike_count_kernel<<<(unsigned)ntr, 64, 0, 0>>>(mask_dev, nw64, ntr, main_end, add_start, counts_dev);
-    D_TRY(hipGetLastError());
-    D_TRY(hipDeviceSynchronize());   // the tile table is freed on return
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipDeviceSynchronize());   // the tile table is freed on return
     return P3D_OK;
 }
 
 int check_spikes(const int* spikes, size_t nspikes, const int* level_start, int nlevels, int ntr, int ns)
 {
-    if (nlevels < 0 || (nspikes > 0 && (!spikes || !level_start || nlevels < 1))) return dfail(P3D_ERR_INVALID, "spike records without levels");
-    if (nlevels > 0 && (level_start[0] != 0 || (size_t)level_start[nlevels] != nspikes)) return dfail(P3D_ERR_INVALID, "level offsets must run from 0 to the number of spikes");
+    if (nlevels < 0 || (nspikes > 0 && (!spikes || !level_start || nlevels < 1))) return fail(P3D_ERR_INVALID, "spike records without levels");
+    if (nlevels > 0 && (level_start[0] != 0 || (size_t)level_start[nlevels] != nspikes)) return fail(P3D_ERR_INVALID, "level offsets must run from 0 to the number of spikes");
     for (int l = 0; l < nlevels; ++l)
-        if (level_start[l + 1] < level_start[l]) return dfail(P3D_ERR_INVALID, "level offsets must not descend");
+        if (level_start[l + 1] < level_start[l]) return fail(P3D_ERR_INVALID, "level offsets must not descend");
     for (size_t i = 0; i < nspikes; ++i) {
         const int* r = spikes + i * SPIKE_INTS;
         const bool ok = r[5] >= 0 && r[5] <= r[0] && r[0] < r[6] && r[6] <= ntr && r[6] - r[5] <= MAXW && r[1] >= 0 && r[1] < r[2] && r[2] <= ns;
-        if (!ok) return dfail(P3D_ERR_INVALID, "spike record %zu outside the section (trace %d, rows %d:%d, columns %d:%d)", i, r[0], r[1], r[2], r[5], r[6]);
+        if (!ok) return fail(P3D_ERR_INVALID, "spike record %zu outside the section (trace %d, rows %d:%d, columns %d:%d)", i, r[0], r[1], r[2], r[5], r[6]);
     }
     return P3D_OK;
 }
 
 int replace_dev(float* section_dev, int ntr, int ns, const int* spikes, size_t nspikes, const int* level_start, int nlevels, int mode, int out, float thr)
 {
-    if (ntr < 1 || ns < 1 || !section_dev) return dfail(P3D_ERR_INVALID, "bad section");
-    if (mode < DSP_MEAN || mode > DSP_RMS) return dfail(P3D_ERR_INVALID, "unknown amplitude mode %d", mode);
-    if (out < OUT_SCALED || out > OUT_MEDIAN) return dfail(P3D_ERR_INVALID, "unknown output amplitude option %d", out);
+    if (ntr < 1 || ns < 1 || !section_dev) return fail(P3D_ERR_INVALID, "bad section");
+    if (mode < DSP_MEAN || mode > DSP_RMS) return fail(P3D_ERR_INVALID, "unknown amplitude mode %d", mode);
+    if (out < OUT_SCALED || out > OUT_MEDIAN) return fail(P3D_ERR_INVALID, "unknown output amplitude option %d", out);
     if (int rc = check_spikes(spikes, nspikes, level_start, nlevels, ntr, ns)) return rc;
     if (nspikes == 0) return P3D_OK;
     DevBuf ds;
-    D_TRY(hipMalloc(&ds.p, nspikes * sizeof(Spike)));
-    D_TRY(hipMemcpy(ds.p, spikes, nspikes * sizeof(Spike), hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&ds.p, nspikes * sizeof(Spike)));
+    P3D_TRY(hipMemcpy(ds.p, spikes, nspikes * sizeof(Spike), hipMemcpyHostToDevice));
     for (int l = 0; l < nlevels; ++l) {   // one batch per level, in stream order
         const int n = level_start[l + 1] - level_start[l];
         if (n == 0) continue;
         despike_replace_kernel<<<(unsigned)n, BS, 0, 0>>>(section_dev, (const Spike*)ds.p + level_start[l], ns, mode, out, thr);
-        D_TRY(hipGetLastError());
+        P3D_TRY(hipGetLastError());
     }
-    D_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
@@ -401,7 +373,7 @@ int p3d_despike_detect_dev(int device, const float* section_dev, int ntr, int ns
                            const int* splits, int nsplits, unsigned long long* mask_dev, int* counts_dev)
 {
     if (int rc = check_window(ntr, ns, w, mode)) return rc;
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     return detect_dev(section_dev, ntr, ns, w, mode, threshold, main_end, add_start, splits, nsplits, mask_dev, counts_dev);
 }
 
@@ -409,40 +381,40 @@ int p3d_despike_detect(int device, const float* section, int ntr, int ns, int w,
                        int nsplits, unsigned long long* mask, int* counts)
 {
     if (int rc = check_window(ntr, ns, w, mode)) return rc;
-    if (!section || !mask || !counts) return dfail(P3D_ERR_INVALID, "NULL buffer");
-    if (int rc = set_device(device)) return rc;
+    if (!section || !mask || !counts) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (int rc = use_device(device)) return rc;
     const size_t nw64 = (size_t)(ns + 63) / 64, nsec = (size_t)ntr * ns * sizeof(float), nmask = (size_t)ntr * nw64 * sizeof(unsigned long long);
     DevBuf da, dm, dc;
-    D_TRY(hipMalloc(&da.p, nsec));
-    D_TRY(hipMalloc(&dm.p, nmask));
-    D_TRY(hipMalloc(&dc.p, 2 * (size_t)ntr * sizeof(int)));
-    D_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&da.p, nsec));
+    P3D_TRY(hipMalloc(&dm.p, nmask));
+    P3D_TRY(hipMalloc(&dc.p, 2 * (size_t)ntr * sizeof(int)));
+    P3D_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
     if (int rc = detect_dev((const float*)da.p, ntr, ns, w, mode, threshold, main_end, add_start, splits, nsplits, (unsigned long long*)dm.p, (int*)dc.p)) return rc;
-    D_TRY(hipMemcpy(mask, dm.p, nmask, hipMemcpyDeviceToHost));
-    D_TRY(hipMemcpy(counts, dc.p, 2 * (size_t)ntr * sizeof(int), hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(mask, dm.p, nmask, hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(counts, dc.p, 2 * (size_t)ntr * sizeof(int), hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
 int p3d_despike_replace_dev(int device, float* section_dev, int ntr, int ns, const int* spikes, size_t nspikes, const int* level_start, int nlevels, int mode,
                             int out, float threshold)
 {
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     return replace_dev(section_dev, ntr, ns, spikes, nspikes, level_start, nlevels, mode, out, threshold);
 }
 
 int p3d_despike_replace(int device, float* section, int ntr, int ns, const int* spikes, size_t nspikes, const int* level_start, int nlevels, int mode, int out,
                         float threshold)
 {
-    if (ntr < 1 || ns < 1 || !section) return dfail(P3D_ERR_INVALID, "bad section");
+    if (ntr < 1 || ns < 1 || !section) return fail(P3D_ERR_INVALID, "bad section");
     if (int rc = check_spikes(spikes, nspikes, level_start, nlevels, ntr, ns)) return rc;
     if (nspikes == 0) return P3D_OK;
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const size_t nsec = (size_t)ntr * ns * sizeof(float);
     DevBuf da;
-    D_TRY(hipMalloc(&da.p, nsec));
-    D_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&da.p, nsec));
+    P3D_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
     if (int rc = replace_dev((float*)da.p, ntr, ns, spikes, nspikes, level_start, nlevels, mode, out, threshold)) return rc;
-    D_TRY(hipMemcpy(section, da.p, nsec, hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(section, da.p, nsec, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 

@@ -17,16 +17,18 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "p3d.h"
 #include "p3d_generic.hpp"
+#include "p3d_host.hpp"
 #include "p3d_internal.hpp"
 #include "p3d_mix64.hpp"
+
+using p3d::fail;
+using p3d::use_device;
 
 namespace {
 
@@ -41,22 +43,6 @@ __device__ __forceinline__ c64 operator*(c64 a, c64 b) { return {a.x * b.x - a.y
 __device__ __forceinline__ c64 operator*(c64 a, double s) { return {a.x * s, a.y * s}; }
 
 constexpr int F64_MAX_N = 5120;
-
-int f64fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define F_TRY(expr)                                                                                   \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) return f64fail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 template <int R>
 __device__ inline void butterfly64(const c64* A, c64* B, const c64* tw, int j, int m, int jm, int j0, int ns, int tstep, int rstep, int dir)
@@ -725,12 +711,12 @@ int fft_pass(p3d_plan64* p, const c64* in, c64* out, int nslices, bool rows, int
     const int n = pl.n;
     const size_t lines = (size_t)nslices * (rows ? p->nil : p->nxl);
     const size_t lds = sizeof(c64) * 2 * (size_t)n;
-    if (lds > 64 * 1024) F_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(line_fft64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 64 * 1024) P3D_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(line_fft64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int threads = 64;
     while (threads < 256 && threads * 4 < n) threads *= 2;
     if (rows) line_fft64<<<dim3((unsigned)lines), threads, lds, p->stream>>>(in, out, p->tw_row, pl, dir, scale, 1, p->nil, p->per(), (size_t)p->nxl, done, p->nil * group);
     else line_fft64<<<dim3((unsigned)lines), threads, lds, p->stream>>>(in, out, p->tw_col, pl, dir, scale, p->nxl, p->nxl, p->per(), (size_t)1, done, p->nxl * group);
-    F_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -773,13 +759,13 @@ int col_pass64(p3d_plan64* p, int nslices, int niter, int iter, int op, const in
         a.n2 = p->nxl; a.nslices = nslices; a.tau = reinterpret_cast<const p3d::mix::c64d*>(p->tau); a.niter = niter; a.iter = iter; a.op = op;
         a.partial = p->partial; a.done = done;
         a.nzflag = (MODE == C64_ITER && p->sparse) ? p->nzflag : nullptr;
-        F_TRY(p->mcol->col(MODE, a, p->stream));
+        P3D_TRY(p->mcol->col(MODE, a, p->stream));
         return P3D_OK;
     }
     auto kern = p->tw_col_lds ? col64_kernel<MODE, true> : col64_kernel<MODE, false>;
-    if (p->lds_col > 64 * 1024) F_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_col));
+    if (p->lds_col > 64 * 1024) P3D_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_col));
     kern<<<dim3(p->tiles_col(), nslices), p->thr_col, p->lds_col, p->stream>>>(p->work, p->tw_col, p->fcol, p->nxl, p->ln_col, p->tw_col_lds, p->tau, niter, iter, op, p->partial, done);
-    F_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -792,18 +778,18 @@ int row_pass64(p3d_plan64* p, int dtype, double* sums_row, int adaptive, int wri
         a.n1 = p->nil; a.nslices = nslices; a.x = p->cur_x; a.dtype = dtype; a.mask = (MODE == R64_FIRST && !adaptive) ? nullptr : p->mask; a.out = p->cur_out;
         a.partial = p->spart; a.adaptive = adaptive; a.write_out = write_out; a.alpha = alpha; a.done = done; a.zero_fill = zero_fill;
         a.nzflag = (MODE != R64_FIRST && p->sparse) ? p->nzflag : nullptr; a.nz_tiles = p->tiles_col(); a.nz_col_t = p->ln_col;
-        F_TRY(p->mrow->row(MODE, a, p->stream));
+        P3D_TRY(p->mrow->row(MODE, a, p->stream));
         fold64_kernel<<<nslices, 64, 0, p->stream>>>(p->spart, sums_row, nslices, p->tiles_row());
-        F_TRY(hipGetLastError());
+        P3D_TRY(hipGetLastError());
         return P3D_OK;
     }
     auto kern = p->tw_row_lds ? row64_kernel<MODE, true> : row64_kernel<MODE, false>;
-    if (p->lds_row > 64 * 1024) F_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_row));
+    if (p->lds_row > 64 * 1024) P3D_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_row));
     kern<<<dim3(p->tiles_row(), nslices), p->thr_row, p->lds_row, p->stream>>>(p->work, p->tw_row, p->frow, p->nil, p->ln_row, p->tw_row_lds, p->cur_x, dtype,
                                                                               (MODE == R64_FIRST && !adaptive) ? nullptr : p->mask, p->cur_out, p->spart, adaptive, write_out, alpha,
                                                                               done, zero_fill);
     fold64_kernel<<<nslices, 64, 0, p->stream>>>(p->spart, sums_row, nslices, p->tiles_row());
-    F_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -822,10 +808,10 @@ bool on_plan_device(const p3d_plan64* p, const void* ptr)
 
 int check64(p3d_plan64* p, int nslices, int dtype)
 {
-    if (!p) return f64fail(P3D_ERR_INVALID, "NULL plan");
-    if (nslices < 1 || nslices > p->max_slices) return f64fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
-    if (dtype != P3D_C128 && dtype != P3D_F64 && dtype != P3D_C64 && dtype != P3D_F32) return f64fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    F_TRY(hipSetDevice(p->device));
+    if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
+    if (nslices < 1 || nslices > p->max_slices) return fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
+    if (dtype != P3D_C128 && dtype != P3D_F64 && dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    P3D_TRY(hipSetDevice(p->device));
     return P3D_OK;
 }
 
@@ -834,7 +820,7 @@ int update(p3d_plan64* p, int dtype, double* sums_row, int mode, int adaptive, i
     update64_kernel<<<dim3(p3d_plan64::BLOCKS, nslices), 256, 0, p->stream>>>(p->work, p->cur_x, dtype, mode == 0 && !adaptive ? nullptr : p->mask, p->cur_out, p->spart, mode,
                                                                               adaptive, write_out, alpha, p->per(), done, zero_fill);
     fold64_kernel<<<nslices, 64, 0, p->stream>>>(p->spart, sums_row, nslices, p3d_plan64::BLOCKS);
-    F_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -860,21 +846,18 @@ int p3d_plan64_destroy(p3d_plan64* p)
 // bare: twiddles and the work buffer only (a plan whose transforms another loop borrows, p3d_shearlet64.hip)
 static int create64(p3d_plan64** out, int device, int nil, int nxl, int max_slices, bool bare)
 {
-    if (!out) return f64fail(P3D_ERR_INVALID, "out is NULL");
+    if (!out) return fail(P3D_ERR_INVALID, "out is NULL");
     *out = nullptr;
-    if (nil < 1 || nxl < 1 || max_slices < 1 || max_slices > 65535) return f64fail(P3D_ERR_INVALID, "nil, nxl, max_slices must be positive (max_slices <= 65535)");
-    if (nil > F64_MAX_N || nxl > F64_MAX_N) return f64fail(P3D_ERR_UNSUPPORTED, "double-precision path: extents up to %d (got %d x %d)", F64_MAX_N, nil, nxl);
-    int ndev = 0;
-    F_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return f64fail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    F_TRY(hipSetDevice(device));
+    if (nil < 1 || nxl < 1 || max_slices < 1 || max_slices > 65535) return fail(P3D_ERR_INVALID, "nil, nxl, max_slices must be positive (max_slices <= 65535)");
+    if (nil > F64_MAX_N || nxl > F64_MAX_N) return fail(P3D_ERR_UNSUPPORTED, "double-precision path: extents up to %d (got %d x %d)", F64_MAX_N, nil, nxl);
+    if (int rc = use_device(device)) return rc;
     p3d_plan64* p = new p3d_plan64;
     p->device = device; p->nil = nil; p->nxl = nxl; p->max_slices = max_slices;
     p->gcol = p3d::gen_make_plan(nil);
     p->grow = p3d::gen_make_plan(nxl);
-    if (p->gcol.nf < 0 || p->grow.nf < 0) { delete p; return f64fail(P3D_ERR_UNSUPPORTED, "slice shape %d x %d cannot be factorised", nil, nxl); }
+    if (p->gcol.nf < 0 || p->grow.nf < 0) { delete p; return fail(P3D_ERR_UNSUPPORTED, "slice shape %d x %d cannot be factorised", nil, nxl); }
     auto bail = [&](const char* what, hipError_t e) {
-        f64fail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        fail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
         std::string keep = p3d_last_error();
         p3d_plan64_destroy(p);
         p3d::set_last_error(keep.c_str());
@@ -951,11 +934,11 @@ int p3d_pocs64_stats(p3d_plan64* p, const void* x, int dtype, int nslices, doubl
 {
     int rc = check64(p, nslices, dtype);
     if (rc) return rc;
-    if (!x || !stats) return f64fail(P3D_ERR_INVALID, "NULL buffer");
+    if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
     if (on_plan_device(p, x)) {
         p->cur_x = x;
     } else {
-        F_TRY(hipMemcpyAsync(p->st_x, x, esize(dtype) * p->per() * nslices, hipMemcpyDefault, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->st_x, x, esize(dtype) * p->per() * nslices, hipMemcpyDefault, p->stream));
         p->cur_x = p->st_x;
     }
     p->cur_out = p->st_out;
@@ -968,11 +951,11 @@ int p3d_pocs64_stats(p3d_plan64* p, const void* x, int dtype, int nslices, doubl
         if ((rc = update(p, dtype, p->partial, 0, 0, 0, 1.0, nslices, nullptr, 0))) return rc;   // w = x (its sums go to a scratch row)
         if ((rc = fft2_64(p, nslices, false, nullptr))) return rc;
         stats64_kernel<<<dim3(p3d_plan64::BLOCKS, nslices), 256, 0, p->stream>>>(p->work, p->partial, p->per());
-        F_TRY(hipGetLastError());
+        P3D_TRY(hipGetLastError());
     }
     std::vector<double> host((size_t)nslices * nblocks * 8);
-    F_TRY(hipMemcpyAsync(host.data(), p->partial, sizeof(double) * host.size(), hipMemcpyDeviceToHost, p->stream));
-    F_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpyAsync(host.data(), p->partial, sizeof(double) * host.size(), hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     for (int s = 0; s < nslices; ++s) {
         double lr = -INFINITY, li = -INFINITY, mx = 0.0, mn = INFINITY, sq = 0.0;
         for (int b = 0; b < nblocks; ++b) {
@@ -995,23 +978,23 @@ int p3d_pocs64_run(p3d_plan64* p, const void* x, int dtype, const double* mask, 
 {
     int rc = check64(p, nslices, dtype);
     if (rc) return rc;
-    if (!x || !mask || !tau || !prm || !out) return f64fail(P3D_ERR_INVALID, "NULL argument");
-    if (prm->niter < 1) return f64fail(P3D_ERR_INVALID, "niter must be >= 1");
-    if (prm->thresh_op < P3D_OP_HARD || prm->thresh_op > P3D_OP_GARROTE) return f64fail(P3D_ERR_UNSUPPORTED, "thresh_op %d: the double-precision path has hard, soft and garrote", prm->thresh_op);
-    if (prm->version < P3D_VER_REGULAR || prm->version > P3D_VER_ADAPTIVE) return f64fail(P3D_ERR_INVALID, "unknown version %d", prm->version);
+    if (!x || !mask || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
+    if (prm->thresh_op < P3D_OP_HARD || prm->thresh_op > P3D_OP_GARROTE) return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d: the double-precision path has hard, soft and garrote", prm->thresh_op);
+    if (prm->version < P3D_VER_REGULAR || prm->version > P3D_VER_ADAPTIVE) return fail(P3D_ERR_INVALID, "unknown version %d", prm->version);
     const int niter = prm->niter;
     const bool early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE;
     const size_t ntau = (size_t)nslices * niter, nsum = (size_t)(niter + 1) * nslices, per = p->per();
     if (p->tau_cap < ntau) {
         if (p->tau) hipFree(p->tau);
         p->tau = nullptr; p->tau_cap = 0;
-        F_TRY(hipMalloc((void**)&p->tau, sizeof(c64) * ntau));
+        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c64) * ntau));
         p->tau_cap = ntau;
     }
     if (p->sums_cap < nsum) {
         if (p->sums) hipFree(p->sums);
         p->sums = nullptr; p->sums_cap = 0;
-        F_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
+        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
         p->sums_cap = nsum;
     }
     std::vector<int> done_h(nslices, 0);
@@ -1024,18 +1007,18 @@ int p3d_pocs64_run(p3d_plan64* p, const void* x, int dtype, const double* mask, 
     if (on_plan_device(p, x)) {
         p->cur_x = x;
     } else {
-        F_TRY(hipMemcpyAsync(p->st_x, x, cube_bytes, hipMemcpyDefault, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->st_x, x, cube_bytes, hipMemcpyDefault, p->stream));
         p->cur_x = p->st_x;
     }
     const char* const xb = static_cast<const char*>(x);
     char* const ob = static_cast<char*>(out);
     const bool direct_out = on_plan_device(p, out) && (ob + cube_bytes <= xb || xb + cube_bytes <= ob);
     p->cur_out = direct_out ? out : p->st_out;
-    F_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * per, hipMemcpyDefault, p->stream));
-    F_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));   // (Re, Im) pairs of doubles: c64's layout
-    F_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    F_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    F_TRY(hipEventRecord(p->ev0, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * per, hipMemcpyDefault, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));   // (Re, Im) pairs of doubles: c64's layout
+    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
+    P3D_TRY(hipEventRecord(p->ev0, p->stream));
     p->sparse = p->nzflag != nullptr;   // (tiles of the spectrum that the threshold empties are neither transformed back, stored nor read again: exact)
     if (p->fused) {
         // two kernels per iteration: rows (inverse transform, re-insertion, forward transform), columns (forward, threshold, inverse)
@@ -1062,16 +1045,16 @@ int p3d_pocs64_run(p3d_plan64* p, const void* x, int dtype, const double* mask, 
         if (early) conv64_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
     }
     }
-    F_TRY(hipGetLastError());
-    F_TRY(hipEventRecord(p->ev1, p->stream));
-    F_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) F_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-    if (!direct_out) F_TRY(hipMemcpyAsync(out, p->st_out, cube_bytes, hipMemcpyDefault, p->stream));
-    F_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipEventRecord(p->ev1, p->stream));
+    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
+    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+    if (!direct_out) P3D_TRY(hipMemcpyAsync(out, p->st_out, cube_bytes, hipMemcpyDefault, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
     if (elapsed_ms) {
         float ms = 0.f;
-        F_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
         *elapsed_ms = ms;
     }
     return P3D_OK;
@@ -1084,11 +1067,11 @@ int p3d_fft2_c128(p3d_plan64* p, const void* in_host, void* out_host, int nslice
 {
     int rc = check64(p, nslices, P3D_C128);
     if (rc) return rc;
-    if (!in_host || !out_host) return f64fail(P3D_ERR_INVALID, "NULL buffer");
+    if (!in_host || !out_host) return fail(P3D_ERR_INVALID, "NULL buffer");
     const size_t bytes = sizeof(c64) * p->per() * nslices;
     p->sparse = false;
     if (!inverse) {
-        F_TRY(hipMemcpyAsync(p->st_x, in_host, bytes, hipMemcpyHostToDevice, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->st_x, in_host, bytes, hipMemcpyHostToDevice, p->stream));
         p->cur_x = p->st_x;
         p->cur_out = p->st_out;
         if (p->fused) {
@@ -1098,25 +1081,25 @@ int p3d_fft2_c128(p3d_plan64* p, const void* in_host, void* out_host, int nslice
             if ((rc = update(p, P3D_C128, p->partial, 0, 0, 0, 1.0, nslices, nullptr, 0))) return rc;
             if ((rc = fft2_64(p, nslices, false, nullptr))) return rc;
         }
-        F_TRY(hipMemcpyAsync(out_host, p->work, bytes, hipMemcpyDeviceToHost, p->stream));
+        P3D_TRY(hipMemcpyAsync(out_host, p->work, bytes, hipMemcpyDeviceToHost, p->stream));
     } else {
-        F_TRY(hipMemcpyAsync(p->work, in_host, bytes, hipMemcpyHostToDevice, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->work, in_host, bytes, hipMemcpyHostToDevice, p->stream));
         if (p->fused) {
-            F_TRY(hipMemsetAsync(p->st_x, 0, bytes, p->stream));
-            F_TRY(hipMemsetAsync(p->mask, 0, sizeof(double) * p->per(), p->stream));
+            P3D_TRY(hipMemsetAsync(p->st_x, 0, bytes, p->stream));
+            P3D_TRY(hipMemsetAsync(p->mask, 0, sizeof(double) * p->per(), p->stream));
             p->cur_x = p->st_x;
             p->cur_out = p->st_out;
             if (p->mcol) rc = p3d::plan64_shear_cols(p, nullptr, nullptr, nslices, 1, 0, 0, 0, 0, 1, 1.0 / p->nil, nullptr, nullptr, 0);
             else rc = fft_pass(p, p->work, p->work, nslices, false, +1, 1.0 / p->nil, nullptr);
             if (rc) return rc;
             if ((rc = row_pass64<R64_LAST>(p, P3D_C128, p->partial, 0, 1, 1.0, nslices, nullptr, 0))) return rc;
-            F_TRY(hipMemcpyAsync(out_host, p->st_out, bytes, hipMemcpyDeviceToHost, p->stream));
+            P3D_TRY(hipMemcpyAsync(out_host, p->st_out, bytes, hipMemcpyDeviceToHost, p->stream));
         } else {
             if ((rc = fft2_64(p, nslices, true, nullptr))) return rc;
-            F_TRY(hipMemcpyAsync(out_host, p->work, bytes, hipMemcpyDeviceToHost, p->stream));
+            P3D_TRY(hipMemcpyAsync(out_host, p->work, bytes, hipMemcpyDeviceToHost, p->stream));
         }
     }
-    F_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     return P3D_OK;
 }
 
@@ -1159,7 +1142,7 @@ int plan64_shear_spread(p3d_plan64* p, const double* psi, void* U, int nb, int n
     a.F = reinterpret_cast<const p3d::mix::c64d*>(p->work); a.psi = psi; a.U = reinterpret_cast<p3d::mix::c64d*>(U);
     a.tab = reinterpret_cast<const p3d::mix::c64d*>(p->tw_mrow); a.n1 = p->nil; a.nb = nb; a.nsh = nsh; a.done = done; a.sup = sup;
     a.sup_groups = (p->nil + p->mrow->row_lines - 1) / p->mrow->row_lines; a.rows = rows > 0 ? rows : p->nil;
-    F_TRY(p->mrow->spread_row(a, p->stream));
+    P3D_TRY(p->mrow->spread_row(a, p->stream));
     return P3D_OK;
 }
 
@@ -1171,7 +1154,7 @@ int plan64_shear_cols(p3d_plan64* p, void* U, const void* tau, int nb, int nsh, 
     a.n2 = p->nxl; a.nslices = nb * nsh; a.nsh = nsh; a.tau = reinterpret_cast<const p3d::mix::c64d*>(tau); a.niter = niter; a.iter = iter; a.op = op;
     a.real_only = real_only; a.mode = mode; a.scale = scale; a.done = done;
     a.sup = sup; a.sup_rows = p->mrow->row_lines; a.sup_groups = (p->nil + a.sup_rows - 1) / a.sup_rows; a.pair = pair;
-    F_TRY(p->mcol->shear_col(a, p->stream));
+    P3D_TRY(p->mcol->shear_col(a, p->stream));
     return P3D_OK;
 }
 
@@ -1181,7 +1164,7 @@ int plan64_shear_gather(p3d_plan64* p, const void* U, const double* psi, int nb,
     a.U = reinterpret_cast<const p3d::mix::c64d*>(U); a.psi = psi; a.F = reinterpret_cast<p3d::mix::c64d*>(p->work);
     a.tab = reinterpret_cast<const p3d::mix::c64d*>(p->tw_mrow); a.n1 = p->nil; a.nb = nb; a.nsh = nsh; a.done = done; a.sup = sup;
     a.sup_groups = (p->nil + p->mrow->row_lines - 1) / p->mrow->row_lines; a.rows = rows > 0 ? rows : p->nil;
-    F_TRY(p->mrow->gather_row(a, p->stream));
+    P3D_TRY(p->mrow->gather_row(a, p->stream));
     return P3D_OK;
 }
 

@@ -1,4 +1,5 @@
 // p3d_internal.hpp -- what the translation units of libp3d_hip.so share beyond the public C ABI (include/p3d.h).
+// The host-side helpers built on it (p3d::fail, P3D_TRY, p3d::DevBuf, p3d::use_device) are in p3d_host.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

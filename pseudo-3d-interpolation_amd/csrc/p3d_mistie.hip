@@ -29,35 +29,16 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <vector>
 
 #include "p3d.h"
-#include "p3d_internal.hpp"
+#include "p3d_host.hpp"
+
+using p3d::DevBuf;
+using p3d::fail;
+using p3d::use_device;
 
 namespace {
-
-int mfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define M_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return mfail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
 
 constexpr int WAVE = 64;
 constexpr int TILE = 64;                        // segments per tile: one per lane
@@ -408,24 +389,15 @@ __global__ void __launch_bounds__(XC_BS) mistie_xcorr_kernel(const float* __rest
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------------
-int set_device(int device)
-{
-    int ndev = 0;
-    M_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return mfail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    M_TRY(hipSetDevice(device));
-    return P3D_OK;
-}
-
 int check_lines(const long long* line_off, int nlines)
 {
-    if (!line_off) return mfail(P3D_ERR_INVALID, "NULL buffer");
-    if (nlines < 1) return mfail(P3D_ERR_INVALID, "at least one line is needed, got %d", nlines);
-    if (line_off[0] != 0) return mfail(P3D_ERR_INVALID, "the vertex offsets must start at 0, got %lld", line_off[0]);
+    if (!line_off) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (nlines < 1) return fail(P3D_ERR_INVALID, "at least one line is needed, got %d", nlines);
+    if (line_off[0] != 0) return fail(P3D_ERR_INVALID, "the vertex offsets must start at 0, got %lld", line_off[0]);
     for (int L = 0; L < nlines; ++L) {
         const long long nv = line_off[L + 1] - line_off[L];
-        if (nv < 0) return mfail(P3D_ERR_INVALID, "the vertex offsets must ascend (line %d)", L);
-        if (nv > INT_MAX) return mfail(P3D_ERR_UNSUPPORTED, "line %d has %lld vertices, more than an int32 index reaches", L, nv);
+        if (nv < 0) return fail(P3D_ERR_INVALID, "the vertex offsets must ascend (line %d)", L);
+        if (nv > INT_MAX) return fail(P3D_ERR_UNSUPPORTED, "line %d has %lld vertices, more than an int32 index reaches", L, nv);
     }
     return P3D_OK;
 }
@@ -433,10 +405,10 @@ int check_lines(const long long* line_off, int nlines)
 int cross_dev(const double* xy, const long long* line_off, int nlines, const int* pairs, int npairs, p3d_mistie_hit* rec, size_t cap, size_t* needed)
 {
     if (int rc = check_lines(line_off, nlines)) return rc;
-    if (!needed || npairs < 0 || (npairs > 0 && !pairs) || (cap > 0 && !rec)) return mfail(P3D_ERR_INVALID, "NULL buffer or negative count");
+    if (!needed || npairs < 0 || (npairs > 0 && !pairs) || (cap > 0 && !rec)) return fail(P3D_ERR_INVALID, "NULL buffer or negative count");
     *needed = 0;
     if (npairs == 0) return P3D_OK;
-    if (!xy) return mfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!xy) return fail(P3D_ERR_INVALID, "NULL buffer");
     std::vector<long long> tile_off(nlines + 1, 0);
     long long most = 0;
     for (int L = 0; L < nlines; ++L) {
@@ -445,31 +417,31 @@ int cross_dev(const double* xy, const long long* line_off, int nlines, const int
     }
     for (int p = 0; p < npairs; ++p) {
         const int i = pairs[2 * p], j = pairs[2 * p + 1];
-        if (i < 0 || j >= nlines || i >= j) return mfail(P3D_ERR_INVALID, "pair %d is (%d, %d): 0 <= i < j < %d is required", p, i, j, nlines);
+        if (i < 0 || j >= nlines || i >= j) return fail(P3D_ERR_INVALID, "pair %d is (%d, %d): 0 <= i < j < %d is required", p, i, j, nlines);
         most = std::max(most, tile_off[i + 1] - tile_off[i]);
     }
     const long long ntiles = tile_off[nlines];
     if (ntiles == 0 || most == 0) return P3D_OK;
-    if (ntiles > 0x7fffffffll) return mfail(P3D_ERR_UNSUPPORTED, "too many segment tiles for one launch (%lld)", ntiles);
+    if (ntiles > 0x7fffffffll) return fail(P3D_ERR_UNSUPPORTED, "too many segment tiles for one launch (%lld)", ntiles);
     const size_t noff = (size_t)(nlines + 1) * sizeof(long long);
     DevBuf dline, dtile, dbox, dpairs, dcount;
-    M_TRY(hipMalloc(&dline.p, noff));
-    M_TRY(hipMalloc(&dtile.p, noff));
-    M_TRY(hipMalloc(&dbox.p, (size_t)ntiles * sizeof(Box)));
-    M_TRY(hipMalloc(&dpairs.p, (size_t)npairs * 2 * sizeof(int)));
-    M_TRY(hipMalloc(&dcount.p, sizeof(unsigned long long)));
-    M_TRY(hipMemcpy(dline.p, line_off, noff, hipMemcpyHostToDevice));
-    M_TRY(hipMemcpy(dtile.p, tile_off.data(), noff, hipMemcpyHostToDevice));
-    M_TRY(hipMemcpy(dpairs.p, pairs, (size_t)npairs * 2 * sizeof(int), hipMemcpyHostToDevice));
-    M_TRY(hipMemset(dcount.p, 0, sizeof(unsigned long long)));
+    P3D_TRY(hipMalloc(&dline.p, noff));
+    P3D_TRY(hipMalloc(&dtile.p, noff));
+    P3D_TRY(hipMalloc(&dbox.p, (size_t)ntiles * sizeof(Box)));
+    P3D_TRY(hipMalloc(&dpairs.p, (size_t)npairs * 2 * sizeof(int)));
+    P3D_TRY(hipMalloc(&dcount.p, sizeof(unsigned long long)));
+    P3D_TRY(hipMemcpy(dline.p, line_off, noff, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(dtile.p, tile_off.data(), noff, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(dpairs.p, pairs, (size_t)npairs * 2 * sizeof(int), hipMemcpyHostToDevice));
+    P3D_TRY(hipMemset(dcount.p, 0, sizeof(unsigned long long)));
     mistie_tilebox_kernel<<<(unsigned)ntiles, WAVE, 0, 0>>>(xy, (const long long*)dline.p, (const long long*)dtile.p, nlines, (Box*)dbox.p);
-    M_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     const dim3 grid((unsigned)npairs, (unsigned)std::min<long long>(most, MAX_GRID_Y));
     mistie_cross_kernel<<<grid, WAVE, 0, 0>>>(xy, (const long long*)dline.p, (const long long*)dtile.p, (const Box*)dbox.p, (const int*)dpairs.p, rec,
                                               (unsigned long long)cap, (unsigned long long*)dcount.p);
-    M_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     unsigned long long got = 0;
-    M_TRY(hipMemcpy(&got, dcount.p, sizeof got, hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(&got, dcount.p, sizeof got, hipMemcpyDeviceToHost));
     *needed = (size_t)got;
     return P3D_OK;
 }
@@ -478,24 +450,24 @@ int nearest_dev(const double* xy, const long long* line_off, int nlines, const d
 {
     if (int rc = check_lines(line_off, nlines)) return rc;
     if (k == 0) return P3D_OK;
-    if (!xy || !pts || !lines || !idx || !dist) return mfail(P3D_ERR_INVALID, "NULL buffer");
-    if (2 * k > 0x7fffffffull) return mfail(P3D_ERR_UNSUPPORTED, "too many crossings for one launch (%zu)", k);
+    if (!xy || !pts || !lines || !idx || !dist) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (2 * k > 0x7fffffffull) return fail(P3D_ERR_UNSUPPORTED, "too many crossings for one launch (%zu)", k);
     const size_t noff = (size_t)(nlines + 1) * sizeof(long long);
     DevBuf doff;
-    M_TRY(hipMalloc(&doff.p, noff));
-    M_TRY(hipMemcpy(doff.p, line_off, noff, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&doff.p, noff));
+    P3D_TRY(hipMemcpy(doff.p, line_off, noff, hipMemcpyHostToDevice));
     mistie_nearest_kernel<<<(unsigned)(2 * k), WAVE, 0, 0>>>(xy, (const long long*)doff.p, nlines, pts, lines, idx, dist);
-    M_TRY(hipGetLastError());
-    M_TRY(hipDeviceSynchronize());              // before the offsets go
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipDeviceSynchronize());              // before the offsets go
     return P3D_OK;
 }
 
 int check_xcorr(size_t ncross, int ns, int path)
 {
-    if (ns < 1) return mfail(P3D_ERR_INVALID, "traces need at least 1 sample, got %d", ns);
-    if (ncross > 0x7fffffffull) return mfail(P3D_ERR_UNSUPPORTED, "too many crossings for one launch (%zu)", ncross);
+    if (ns < 1) return fail(P3D_ERR_INVALID, "traces need at least 1 sample, got %d", ns);
+    if (ncross > 0x7fffffffull) return fail(P3D_ERR_UNSUPPORTED, "too many crossings for one launch (%zu)", ncross);
     if (path != P3D_MISTIE_PATH_AUTO && path != P3D_MISTIE_PATH_LDS && path != P3D_MISTIE_PATH_GLOBAL)
-        return mfail(P3D_ERR_INVALID, "unknown path %d", path);
+        return fail(P3D_ERR_INVALID, "unknown path %d", path);
     return P3D_OK;
 }
 
@@ -504,25 +476,25 @@ int xcorr_dev(const float* a, const float* b, size_t ncross, int ns, const int* 
               int* status)
 {
     if (ncross == 0) return P3D_OK;
-    if (!a || !b || !ranges || !shift || !coeff || !count || !status) return mfail(P3D_ERR_INVALID, "NULL buffer");
-    if (max_len < 0 || max_len > ns) return mfail(P3D_ERR_INVALID, "the longest window (%d samples) does not fit traces of %d samples", max_len, ns);
+    if (!a || !b || !ranges || !shift || !coeff || !count || !status) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (max_len < 0 || max_len > ns) return fail(P3D_ERR_INVALID, "the longest window (%d samples) does not fit traces of %d samples", max_len, ns);
     if (path == P3D_MISTIE_PATH_LDS && max_len > LDS_SAMPLES)
-        return mfail(P3D_ERR_UNSUPPORTED, "windows of up to %d samples fit the LDS, got %d", LDS_SAMPLES, max_len);
+        return fail(P3D_ERR_UNSUPPORTED, "windows of up to %d samples fit the LDS, got %d", LDS_SAMPLES, max_len);
     const bool lds = path == P3D_MISTIE_PATH_LDS || (path == P3D_MISTIE_PATH_AUTO && max_len <= LDS_SAMPLES);
     if (lds) {
         mistie_xcorr_kernel<true><<<(unsigned)ncross, XC_BS, (size_t)2 * std::max(max_len, 1) * sizeof(float), 0>>>(a, b, ns, ranges, max_len, nullptr, shift, coeff,
                                                                                                                   count, status);
-        M_TRY(hipGetLastError());
+        P3D_TRY(hipGetLastError());
         return P3D_OK;
     }
     DevBuf own;
     if (!work) {
-        M_TRY(hipMalloc(&own.p, ncross * 2 * (size_t)ns * sizeof(float)));
+        P3D_TRY(hipMalloc(&own.p, ncross * 2 * (size_t)ns * sizeof(float)));
         work = (float*)own.p;
     }
     mistie_xcorr_kernel<false><<<(unsigned)ncross, XC_BS, 0, 0>>>(a, b, ns, ranges, max_len, work, shift, coeff, count, status);
-    M_TRY(hipGetLastError());
-    M_TRY(hipDeviceSynchronize());              // before an own work buffer goes
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipDeviceSynchronize());              // before an own work buffer goes
     return P3D_OK;
 }
 
@@ -533,16 +505,16 @@ extern "C" {
 int p3d_mistie_cross_dev(int device, const double* xy_dev, const long long* line_off, int nlines, const int* pairs, int npairs, p3d_mistie_hit* hits_dev,
                          size_t capacity, size_t* needed)
 {
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (int rc = cross_dev(xy_dev, line_off, nlines, pairs, npairs, hits_dev, capacity, needed)) return rc;
-    M_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_mistie_nearest_dev(int device, const double* xy_dev, const long long* line_off, int nlines, const double* points_dev, const int* lines_dev,
                            size_t ncross, int* index_dev, double* dist_dev)
 {
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (int rc = nearest_dev(xy_dev, line_off, nlines, points_dev, lines_dev, ncross, index_dev, dist_dev)) return rc;
     return P3D_OK;
 }
@@ -551,9 +523,9 @@ int p3d_mistie_xcorr_dev(int device, const float* a_dev, const float* b_dev, siz
                          float* work_dev, int* shift_dev, double* coeff_dev, int* n_dev, int* status_dev)
 {
     if (int rc = check_xcorr(ncross, ns, path)) return rc;
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (int rc = xcorr_dev(a_dev, b_dev, ncross, ns, ranges_dev, max_len, path, work_dev, shift_dev, coeff_dev, n_dev, status_dev)) return rc;
-    M_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
@@ -561,18 +533,18 @@ int p3d_mistie_cross(int device, const double* xy, const long long* line_off, in
                      size_t* needed)
 {
     if (int rc = check_lines(line_off, nlines)) return rc;
-    if (!xy && line_off[nlines] > 0) return mfail(P3D_ERR_INVALID, "NULL buffer");
-    if (int rc = set_device(device)) return rc;
+    if (!xy && line_off[nlines] > 0) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (int rc = use_device(device)) return rc;
     const size_t nxy = (size_t)line_off[nlines] * 2 * sizeof(double);
     DevBuf dxy, drec;
-    M_TRY(hipMalloc(&dxy.p, std::max(nxy, sizeof(double))));
-    M_TRY(hipMalloc(&drec.p, std::max(capacity, (size_t)1) * sizeof(p3d_mistie_hit)));
-    if (nxy) M_TRY(hipMemcpy(dxy.p, xy, nxy, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dxy.p, std::max(nxy, sizeof(double))));
+    P3D_TRY(hipMalloc(&drec.p, std::max(capacity, (size_t)1) * sizeof(p3d_mistie_hit)));
+    if (nxy) P3D_TRY(hipMemcpy(dxy.p, xy, nxy, hipMemcpyHostToDevice));
     if (int rc = cross_dev((const double*)dxy.p, line_off, nlines, pairs, npairs, (p3d_mistie_hit*)drec.p, capacity, needed)) return rc;
     const size_t got = std::min(*needed, capacity);
     if (got) {
-        if (!hits) return mfail(P3D_ERR_INVALID, "NULL buffer");
-        M_TRY(hipMemcpy(hits, drec.p, got * sizeof(p3d_mistie_hit), hipMemcpyDeviceToHost));
+        if (!hits) return fail(P3D_ERR_INVALID, "NULL buffer");
+        P3D_TRY(hipMemcpy(hits, drec.p, got * sizeof(p3d_mistie_hit), hipMemcpyDeviceToHost));
     }
     return P3D_OK;
 }
@@ -582,25 +554,25 @@ int p3d_mistie_nearest(int device, const double* xy, const long long* line_off, 
 {
     if (int rc = check_lines(line_off, nlines)) return rc;
     if (ncross == 0) return P3D_OK;
-    if (!xy || !points || !lines || !index || !dist) return mfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!xy || !points || !lines || !index || !dist) return fail(P3D_ERR_INVALID, "NULL buffer");
     for (size_t w = 0; w < 2 * ncross; ++w)
-        if (lines[w] < 0 || lines[w] >= nlines) return mfail(P3D_ERR_INVALID, "crossing %zu names line %d of %d", w / 2, lines[w], nlines);
-    if (int rc = set_device(device)) return rc;
+        if (lines[w] < 0 || lines[w] >= nlines) return fail(P3D_ERR_INVALID, "crossing %zu names line %d of %d", w / 2, lines[w], nlines);
+    if (int rc = use_device(device)) return rc;
     const size_t nxy = (size_t)line_off[nlines] * 2 * sizeof(double);
     DevBuf dxy, dpts, dlines, didx, ddist;
-    M_TRY(hipMalloc(&dxy.p, std::max(nxy, sizeof(double))));
-    M_TRY(hipMalloc(&dpts.p, ncross * 2 * sizeof(double)));
-    M_TRY(hipMalloc(&dlines.p, ncross * 2 * sizeof(int)));
-    M_TRY(hipMalloc(&didx.p, ncross * 2 * sizeof(int)));
-    M_TRY(hipMalloc(&ddist.p, ncross * 2 * sizeof(double)));
-    if (nxy) M_TRY(hipMemcpy(dxy.p, xy, nxy, hipMemcpyHostToDevice));
-    M_TRY(hipMemcpy(dpts.p, points, ncross * 2 * sizeof(double), hipMemcpyHostToDevice));
-    M_TRY(hipMemcpy(dlines.p, lines, ncross * 2 * sizeof(int), hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dxy.p, std::max(nxy, sizeof(double))));
+    P3D_TRY(hipMalloc(&dpts.p, ncross * 2 * sizeof(double)));
+    P3D_TRY(hipMalloc(&dlines.p, ncross * 2 * sizeof(int)));
+    P3D_TRY(hipMalloc(&didx.p, ncross * 2 * sizeof(int)));
+    P3D_TRY(hipMalloc(&ddist.p, ncross * 2 * sizeof(double)));
+    if (nxy) P3D_TRY(hipMemcpy(dxy.p, xy, nxy, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(dpts.p, points, ncross * 2 * sizeof(double), hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(dlines.p, lines, ncross * 2 * sizeof(int), hipMemcpyHostToDevice));
     if (int rc = nearest_dev((const double*)dxy.p, line_off, nlines, (const double*)dpts.p, (const int*)dlines.p, ncross, (int*)didx.p,
                              (double*)ddist.p))
         return rc;
-    M_TRY(hipMemcpy(index, didx.p, ncross * 2 * sizeof(int), hipMemcpyDeviceToHost));
-    M_TRY(hipMemcpy(dist, ddist.p, ncross * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(index, didx.p, ncross * 2 * sizeof(int), hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(dist, ddist.p, ncross * 2 * sizeof(double), hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
@@ -609,33 +581,33 @@ int p3d_mistie_xcorr(int device, const float* a, const float* b, size_t ncross, 
 {
     if (int rc = check_xcorr(ncross, ns, path)) return rc;
     if (ncross == 0) return P3D_OK;
-    if (!a || !b || !ranges || !shift || !coeff || !n || !status) return mfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!a || !b || !ranges || !shift || !coeff || !n || !status) return fail(P3D_ERR_INVALID, "NULL buffer");
     int max_len = 0;
     for (size_t c = 0; c < ncross; ++c) {       // windows outside the trace get their status from the kernel, which reads nothing there
         const int la = ranges[4 * c + 1], lb = ranges[4 * c + 3];
         if (la >= 0 && la <= ns) max_len = std::max(max_len, la);
         if (lb >= 0 && lb <= ns) max_len = std::max(max_len, lb);
     }
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const size_t nsec = ncross * (size_t)ns * sizeof(float);
     DevBuf da, db, dr, ds, dc, dn, dst;
-    M_TRY(hipMalloc(&da.p, nsec));
-    M_TRY(hipMalloc(&db.p, nsec));
-    M_TRY(hipMalloc(&dr.p, ncross * 4 * sizeof(int)));
-    M_TRY(hipMalloc(&ds.p, ncross * sizeof(int)));
-    M_TRY(hipMalloc(&dc.p, ncross * sizeof(double)));
-    M_TRY(hipMalloc(&dn.p, ncross * sizeof(int)));
-    M_TRY(hipMalloc(&dst.p, ncross * sizeof(int)));
-    M_TRY(hipMemcpy(da.p, a, nsec, hipMemcpyHostToDevice));
-    M_TRY(hipMemcpy(db.p, b, nsec, hipMemcpyHostToDevice));
-    M_TRY(hipMemcpy(dr.p, ranges, ncross * 4 * sizeof(int), hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&da.p, nsec));
+    P3D_TRY(hipMalloc(&db.p, nsec));
+    P3D_TRY(hipMalloc(&dr.p, ncross * 4 * sizeof(int)));
+    P3D_TRY(hipMalloc(&ds.p, ncross * sizeof(int)));
+    P3D_TRY(hipMalloc(&dc.p, ncross * sizeof(double)));
+    P3D_TRY(hipMalloc(&dn.p, ncross * sizeof(int)));
+    P3D_TRY(hipMalloc(&dst.p, ncross * sizeof(int)));
+    P3D_TRY(hipMemcpy(da.p, a, nsec, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(db.p, b, nsec, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(dr.p, ranges, ncross * 4 * sizeof(int), hipMemcpyHostToDevice));
     if (int rc = xcorr_dev((const float*)da.p, (const float*)db.p, ncross, ns, (const int*)dr.p, max_len, path, nullptr, (int*)ds.p, (double*)dc.p, (int*)dn.p,
                            (int*)dst.p))
         return rc;
-    M_TRY(hipMemcpy(shift, ds.p, ncross * sizeof(int), hipMemcpyDeviceToHost));
-    M_TRY(hipMemcpy(coeff, dc.p, ncross * sizeof(double), hipMemcpyDeviceToHost));
-    M_TRY(hipMemcpy(n, dn.p, ncross * sizeof(int), hipMemcpyDeviceToHost));
-    M_TRY(hipMemcpy(status, dst.p, ncross * sizeof(int), hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(shift, ds.p, ncross * sizeof(int), hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(coeff, dc.p, ncross * sizeof(double), hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(n, dn.p, ncross * sizeof(int), hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(status, dst.p, ncross * sizeof(int), hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 

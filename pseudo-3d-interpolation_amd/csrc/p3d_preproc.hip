@@ -21,53 +21,25 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <vector>
 
 #include "p3d.h"
+#include "p3d_host.hpp"
 #include "p3d_internal.hpp"
 
 using p3d::c32;
+using p3d::DevBuf;
+using p3d::fail;
+using p3d::use_device;
 
 namespace {
 
 constexpr int FFT_MAX_N = 10240;   // GEN_MAX_N of p3d_generic.hpp: the longest line of the any-length FFT
 
-int pfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define P_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return pfail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
-
-int select_device(int device)
-{
-    int ndev = 0;
-    P_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return pfail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    P_TRY(hipSetDevice(device));
-    return P3D_OK;
-}
-
 int check_shape(size_t nt, size_t ntr)
 {
-    if (nt < 1 || ntr < 1) return pfail(P3D_ERR_INVALID, "bad shape (nt %zu, ntraces %zu)", nt, ntr);
-    if (ntr > 2147483647u) return pfail(P3D_ERR_INVALID, "too many traces for one call: split the cube");
+    if (nt < 1 || ntr < 1) return fail(P3D_ERR_INVALID, "bad shape (nt %zu, ntraces %zu)", nt, ntr);
+    if (ntr > 2147483647u) return fail(P3D_ERR_INVALID, "too many traces for one call: split the cube");
     return P3D_OK;
 }
 
@@ -366,11 +338,11 @@ __global__ void __launch_bounds__(TPB) c32_to_real_kernel(const c32* __restrict_
 int gain_pass(const float* x, float* out, size_t nt, size_t ntr, GainArgs a)
 {
     if (!a.mask) {
-        if (x != out) P_TRY(hipMemcpy(out, x, sizeof(float) * nt * ntr, hipMemcpyDeviceToDevice));
+        if (x != out) P3D_TRY(hipMemcpy(out, x, sizeof(float) * nt * ntr, hipMemcpyDeviceToDevice));
         return P3D_OK;
     }
     pre_gain_kernel<<<grid2(ntr, nt), TPB>>>(x, out, (long long)nt, (long long)ntr, a);
-    P_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -382,42 +354,42 @@ extern "C" {
 
 int p3d_pre_reduce_dev(int device, const float* x, size_t nt, size_t ntr, int kind, float* res)
 {
-    if (!x || !res) return pfail(P3D_ERR_INVALID, "NULL buffer");
-    if (kind < 0 || kind > 2) return pfail(P3D_ERR_INVALID, "unknown reduction %d (0 = rms, 1 = max, 2 = rms without the 0 -> 1 guard)", kind);
+    if (!x || !res) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (kind < 0 || kind > 2) return fail(P3D_ERR_INVALID, "unknown reduction %d (0 = rms, 1 = max, 2 = rms without the 0 -> 1 guard)", kind);
     int rc = check_shape(nt, ntr);
-    if (rc || (rc = select_device(device))) return rc;
+    if (rc || (rc = use_device(device))) return rc;
     pre_reduce_kernel<<<(unsigned)((ntr + TPB - 1) / TPB), TPB>>>(x, (long long)nt, (long long)ntr, kind, res);
-    P_TRY(hipGetLastError());
-    P_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_pre_balance_dev(int device, const float* x, size_t nt, size_t ntr, int kind, float* out, float* ref)
 {
-    if (!x || !out || !ref) return pfail(P3D_ERR_INVALID, "NULL buffer");
-    if (kind != 0 && kind != 1) return pfail(P3D_ERR_INVALID, "unknown reference amplitude %d (0 = rms, 1 = max)", kind);
+    if (!x || !out || !ref) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (kind != 0 && kind != 1) return fail(P3D_ERR_INVALID, "unknown reference amplitude %d (0 = rms, 1 = max)", kind);
     int rc = p3d_pre_reduce_dev(device, x, nt, ntr, kind, ref);
     if (rc) return rc;
     GainArgs a{};
     a.mask = 1u << S_DIV;
     a.div = ref;
     if ((rc = gain_pass(x, out, nt, ntr, a))) return rc;
-    P_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_pre_gain_dev(int device, const float* x, size_t nt, size_t ntr, const double* prm, const double* curves, float* out, float* work)
 {
-    if (!x || !out || !prm) return pfail(P3D_ERR_INVALID, "NULL buffer");
-    if (x == out) return pfail(P3D_ERR_INVALID, "x and out must be different buffers");
+    if (!x || !out || !prm) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (x == out) return fail(P3D_ERR_INVALID, "x and out must be different buffers");
     int rc = check_shape(nt, ntr);
-    if (rc || (rc = select_device(device))) return rc;
+    if (rc || (rc = use_device(device))) return rc;
     const unsigned flags = (unsigned)prm[P3D_GAIN_FLAGS];
-    if (flags & ~((1u << P3D_GAIN_NBITS) - 1u)) return pfail(P3D_ERR_INVALID, "unknown gain flags 0x%x", flags);
+    if (flags & ~((1u << P3D_GAIN_NBITS) - 1u)) return fail(P3D_ERR_INVALID, "unknown gain flags 0x%x", flags);
     const bool agc = flags & P3D_GAIN_F_AGC;
-    if (agc && !work) return pfail(P3D_ERR_INVALID, "AGC needs a work buffer of nt x ntraces floats");
+    if (agc && !work) return fail(P3D_ERR_INVALID, "AGC needs a work buffer of nt x ntraces floats");
     const bool need_curves = flags & (P3D_GAIN_F_TPOW | P3D_GAIN_F_EPOW | P3D_GAIN_F_LINEAR | P3D_GAIN_F_PGC);
-    if (need_curves && !curves) return pfail(P3D_ERR_INVALID, "gain curves missing");
+    if (need_curves && !curves) return fail(P3D_ERR_INVALID, "gain curves missing");
 
     // tables: tpow, epow, linear (float64) and pgc (float32) curves [nt]; per-trace quantile (double) and rms (float)
     DevBuf dcur, dq, drms;
@@ -433,10 +405,10 @@ int p3d_pre_gain_dev(int device, const float* x, size_t nt, size_t ntr, const do
         std::vector<double> host(curves, curves + 4 * nt);
         std::vector<float> pgc(nt);
         for (size_t t = 0; t < nt; ++t) pgc[t] = (float)curves[3 * nt + t];
-        P_TRY(hipMalloc(&dcur.p, sizeof(double) * 3 * nt + sizeof(float) * nt));
-        P_TRY(hipMemcpy(dcur.p, host.data(), sizeof(double) * 3 * nt, hipMemcpyHostToDevice));
+        P3D_TRY(hipMalloc(&dcur.p, sizeof(double) * 3 * nt + sizeof(float) * nt));
+        P3D_TRY(hipMemcpy(dcur.p, host.data(), sizeof(double) * 3 * nt, hipMemcpyHostToDevice));
         float* dp = (float*)((double*)dcur.p + 3 * nt);
-        P_TRY(hipMemcpy(dp, pgc.data(), sizeof(float) * nt, hipMemcpyHostToDevice));
+        P3D_TRY(hipMemcpy(dp, pgc.data(), sizeof(float) * nt, hipMemcpyHostToDevice));
         a.tpow = (const double*)dcur.p;
         a.epow = a.tpow + nt;
         a.linear = a.tpow + 2 * nt;
@@ -467,7 +439,7 @@ int p3d_pre_gain_dev(int device, const float* x, size_t nt, size_t ntr, const do
         b.mask = want & range_mask(lo, hi);
         if (!b.mask) return P3D_OK;
         float* d = dst_for(cur);
-        if (!d) return pfail(P3D_ERR_INVALID, "this gain needs a work buffer of nt x ntraces floats");
+        if (!d) return fail(P3D_ERR_INVALID, "this gain needs a work buffer of nt x ntraces floats");
         int r = gain_pass(cur, d, nt, ntr, b);
         if (r) return r;
         cur = d;
@@ -485,47 +457,47 @@ int p3d_pre_gain_dev(int device, const float* x, size_t nt, size_t ntr, const do
     if (want & (1u << S_QCLIP)) {
         if ((rc = run(lo, S_QCLIP))) return rc;
         lo = S_QCLIP;
-        P_TRY(hipMalloc(&dq.p, sizeof(double) * ntr));
+        P3D_TRY(hipMalloc(&dq.p, sizeof(double) * ntr));
         pre_quantile_kernel<<<(unsigned)((ntr + TPB - 1) / TPB), TPB>>>(cur, (long long)nt, (long long)ntr, prm[P3D_GAIN_QCLIP], (double*)dq.p);
-        P_TRY(hipGetLastError());
+        P3D_TRY(hipGetLastError());
         a.qthr = (const double*)dq.p;
     }
     if (want & (1u << S_DIV)) {
         if ((rc = run(lo, S_DIV))) return rc;
         lo = S_DIV;
-        P_TRY(hipMalloc(&drms.p, sizeof(float) * ntr));
+        P3D_TRY(hipMalloc(&drms.p, sizeof(float) * ntr));
         pre_reduce_kernel<<<(unsigned)((ntr + TPB - 1) / TPB), TPB>>>(cur, (long long)nt, (long long)ntr, 0, (float*)drms.p);
-        P_TRY(hipGetLastError());
+        P3D_TRY(hipGetLastError());
         a.div = (const float*)drms.p;
     }
     if ((rc = run(lo, S_COUNT))) return rc;
     if (cur == x) {
-        P_TRY(hipMemcpy(out, x, sizeof(float) * nt * ntr, hipMemcpyDeviceToDevice));
+        P3D_TRY(hipMemcpy(out, x, sizeof(float) * nt * ntr, hipMemcpyDeviceToDevice));
     } else if (cur != out) {
-        P_TRY(hipMemcpy(out, cur, sizeof(float) * nt * ntr, hipMemcpyDeviceToDevice));
+        P3D_TRY(hipMemcpy(out, cur, sizeof(float) * nt * ntr, hipMemcpyDeviceToDevice));
     }
-    P_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_pre_sosfiltfilt_dev(int device, const float* x, size_t nt, size_t ntr, int nsec, const double* sos, const double* zi, int padlen, float* out,
                             float* work)
 {
-    if (!x || !out || !sos || !zi) return pfail(P3D_ERR_INVALID, "NULL buffer");
-    if (x == out) return pfail(P3D_ERR_INVALID, "x and out must be different buffers");
-    if (nsec < 1) return pfail(P3D_ERR_INVALID, "%d sections", nsec);
-    if (padlen < 0) return pfail(P3D_ERR_INVALID, "padlen %d", padlen);
+    if (!x || !out || !sos || !zi) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (x == out) return fail(P3D_ERR_INVALID, "x and out must be different buffers");
+    if (nsec < 1) return fail(P3D_ERR_INVALID, "%d sections", nsec);
+    if (padlen < 0) return fail(P3D_ERR_INVALID, "padlen %d", padlen);
     int rc = check_shape(nt, ntr);
-    if (rc || (rc = select_device(device))) return rc;
+    if (rc || (rc = use_device(device))) return rc;
     if (nt <= (size_t)padlen)
-        return pfail(P3D_ERR_INVALID, "The length of the input vector x must be greater than padlen, which is %d.", padlen);
+        return fail(P3D_ERR_INVALID, "The length of the input vector x must be greater than padlen, which is %d.", padlen);
     for (int k = 0; k < nsec; ++k)
-        if (sos[6 * k + 3] != 1.0) return pfail(P3D_ERR_INVALID, "section %d: a0 must be 1", k);
+        if (sos[6 * k + 3] != 1.0) return fail(P3D_ERR_INVALID, "section %d: a0 must be 1", k);
     const size_t ne = nt + 2 * (size_t)padlen;
     DevBuf dtmp, dy0;
     float* tmp = work;
     if (!tmp) {
-        P_TRY(hipMalloc(&dtmp.p, sizeof(float) * ne * ntr));
+        P3D_TRY(hipMalloc(&dtmp.p, sizeof(float) * ne * ntr));
         tmp = (float*)dtmp.p;
     }
     const int ngroups = (nsec + SOS_GROUP - 1) / SOS_GROUP;
@@ -545,69 +517,69 @@ int p3d_pre_sosfiltfilt_dev(int device, const float* x, size_t nt, size_t ntr, i
     const dim3 g1((unsigned)((ntr + TPB - 1) / TPB));
     const long long lnt = (long long)nt, lntr = (long long)ntr, ledge = padlen;
     if (ngroups == 1) {
-        P_TRY(launch_ns<FusedL>(gsize[0], g1, x, tmp, out, groups[0], lnt, lntr, ledge));
+        P3D_TRY(launch_ns<FusedL>(gsize[0], g1, x, tmp, out, groups[0], lnt, lntr, ledge));
     } else {
-        P_TRY(hipMalloc(&dy0.p, sizeof(double) * ntr));
+        P3D_TRY(hipMalloc(&dy0.p, sizeof(double) * ntr));
         double* y0 = (double*)dy0.p;
         for (int g = 0; g < ngroups; ++g)
-            P_TRY(launch_ns<FwdL>(gsize[g], g1, x, tmp, y0, groups[g], lnt, lntr, ledge, (int)(g == 0), (int)(g == ngroups - 1)));
+            P3D_TRY(launch_ns<FwdL>(gsize[g], g1, x, tmp, y0, groups[g], lnt, lntr, ledge, (int)(g == 0), (int)(g == ngroups - 1)));
         for (int g = 0; g < ngroups; ++g)
-            P_TRY(launch_ns<BwdL>(gsize[g], g1, tmp, out, (const double*)y0, groups[g], lnt, lntr, ledge, (int)(g == ngroups - 1)));
+            P3D_TRY(launch_ns<BwdL>(gsize[g], g1, tmp, out, (const double*)y0, groups[g], lnt, lntr, ledge, (int)(g == ngroups - 1)));
     }
-    P_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_pre_upfirdn_dev(int device, const float* x, size_t nt, size_t ntr, const double* h, int nh, int up, int down, long long pre_remove,
                         size_t nout, float* out)
 {
-    if (!x || !out || !h) return pfail(P3D_ERR_INVALID, "NULL buffer");
-    if (x == out) return pfail(P3D_ERR_INVALID, "x and out must be different buffers");
-    if (nh < 1 || up < 1 || down < 1 || pre_remove < 0 || nout < 1) return pfail(P3D_ERR_INVALID, "bad upfirdn parameters");
+    if (!x || !out || !h) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (x == out) return fail(P3D_ERR_INVALID, "x and out must be different buffers");
+    if (nh < 1 || up < 1 || down < 1 || pre_remove < 0 || nout < 1) return fail(P3D_ERR_INVALID, "bad upfirdn parameters");
     int rc = check_shape(nt, ntr);
-    if (rc || (rc = select_device(device))) return rc;
+    if (rc || (rc = use_device(device))) return rc;
     DevBuf dh;
-    P_TRY(hipMalloc(&dh.p, sizeof(double) * nh));
-    P_TRY(hipMemcpy(dh.p, h, sizeof(double) * nh, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dh.p, sizeof(double) * nh));
+    P3D_TRY(hipMemcpy(dh.p, h, sizeof(double) * nh, hipMemcpyHostToDevice));
     pre_upfirdn_kernel<<<grid2(ntr, nout), TPB>>>(x, out, (const double*)dh.p, nh, up, down, pre_remove, (long long)nt, (long long)nout, (long long)ntr);
-    P_TRY(hipGetLastError());
-    P_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_pre_spectral_dev(int device, const float* x, size_t nt, size_t ntr, int num, const int* src, const float* fac, int modulus, double s1,
                          double s2, float* out, void* work)
 {
-    if (!x || !out || !src || !fac) return pfail(P3D_ERR_INVALID, "NULL buffer");
-    if (num < 1) return pfail(P3D_ERR_INVALID, "output length %d", num);
+    if (!x || !out || !src || !fac) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (num < 1) return fail(P3D_ERR_INVALID, "output length %d", num);
     int rc = check_shape(nt, ntr);
-    if (rc || (rc = select_device(device))) return rc;
+    if (rc || (rc = use_device(device))) return rc;
     if (!p3d::axis0_fft_supported((int)nt) || nt > 2147483647u)
-        return pfail(P3D_ERR_UNSUPPORTED, "a trace of %zu samples: FFT lengths up to %d are supported", nt, FFT_MAX_N);
-    if (!p3d::axis0_fft_supported(num)) return pfail(P3D_ERR_UNSUPPORTED, "an output trace of %d samples: FFT lengths up to %d are supported", num, FFT_MAX_N);
+        return fail(P3D_ERR_UNSUPPORTED, "a trace of %zu samples: FFT lengths up to %d are supported", nt, FFT_MAX_N);
+    if (!p3d::axis0_fft_supported(num)) return fail(P3D_ERR_UNSUPPORTED, "an output trace of %d samples: FFT lengths up to %d are supported", num, FFT_MAX_N);
     for (int k = 0; k < num; ++k)
-        if (src[k] >= 0 && (size_t)(src[k] >> 2) >= nt) return pfail(P3D_ERR_INVALID, "source bin %d of output bin %d outside 0..%zu", src[k] >> 2, k, nt - 1);
+        if (src[k] >= 0 && (size_t)(src[k] >> 2) >= nt) return fail(P3D_ERR_INVALID, "source bin %d of output bin %d outside 0..%zu", src[k] >> 2, k, nt - 1);
     DevBuf dw, dsrc, dfac;
     c32* wx = (c32*)work;
     if (!wx) {
-        P_TRY(hipMalloc(&dw.p, sizeof(c32) * ((size_t)nt + (size_t)num) * ntr));
+        P3D_TRY(hipMalloc(&dw.p, sizeof(c32) * ((size_t)nt + (size_t)num) * ntr));
         wx = (c32*)dw.p;
     }
     c32* wz = wx + nt * ntr;
-    P_TRY(hipMalloc(&dsrc.p, sizeof(int) * num));
-    P_TRY(hipMalloc(&dfac.p, sizeof(float) * num));
-    P_TRY(hipMemcpy(dsrc.p, src, sizeof(int) * num, hipMemcpyHostToDevice));
-    P_TRY(hipMemcpy(dfac.p, fac, sizeof(float) * num, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&dsrc.p, sizeof(int) * num));
+    P3D_TRY(hipMalloc(&dfac.p, sizeof(float) * num));
+    P3D_TRY(hipMemcpy(dsrc.p, src, sizeof(int) * num, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(dfac.p, fac, sizeof(float) * num, hipMemcpyHostToDevice));
     const long long n_in = (long long)(nt * ntr), n_out = (long long)num * (long long)ntr;
     real_to_c32_kernel<<<(unsigned)((n_in + TPB - 1) / TPB), TPB>>>(x, wx, n_in);
-    P_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     if ((rc = p3d::axis0_fft(device, wx, (int)nt, ntr, 0))) return rc;
     spec_remap_kernel<<<grid2(ntr, (size_t)num), TPB>>>(wx, wz, (const int*)dsrc.p, (const float*)dfac.p, num, (long long)ntr);
-    P_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     if ((rc = p3d::axis0_fft(device, wz, num, ntr, 1))) return rc;
     c32_to_real_kernel<<<(unsigned)((n_out + TPB - 1) / TPB), TPB>>>(wz, out, n_out, (float)s1, (float)s2, modulus);
-    P_TRY(hipGetLastError());
-    P_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 

@@ -15,35 +15,20 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "p3d.h"
 #include "p3d_fft.hpp"
+#include "p3d_host.hpp"
 #include "p3d_internal.hpp"
 #include "p3d_shrink.hpp"
 
 using p3d::c32;
+using p3d::fail;
 
 namespace {
 
-int sfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define S_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return sfail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 #define S_RC(expr)                \
     do {                          \
         int rc_ = (expr);         \
@@ -269,10 +254,10 @@ extern "C" int p3d_shearlet_plan_destroy(p3d_splan* p)
 
 extern "C" int p3d_shearlet_plan_create(p3d_splan** out, int device, int nil, int nxl, int nsh, const float* psi, int max_slices)
 {
-    if (!out || !psi) return sfail(P3D_ERR_INVALID, "NULL argument");
+    if (!out || !psi) return fail(P3D_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    if (nil < 1 || nxl < 1 || nsh < 1 || max_slices < 1) return sfail(P3D_ERR_INVALID, "bad shape / batch size");
-    if ((long long)max_slices * nsh > 65535) return sfail(P3D_ERR_INVALID, "max_slices * nsh = %lld exceeds 65535", (long long)max_slices * nsh);
+    if (nil < 1 || nxl < 1 || nsh < 1 || max_slices < 1) return fail(P3D_ERR_INVALID, "bad shape / batch size");
+    if ((long long)max_slices * nsh > 65535) return fail(P3D_ERR_INVALID, "max_slices * nsh = %lld exceeds 65535", (long long)max_slices * nsh);
     p3d_splan* p = new p3d_splan;
     p->device = device; p->nil = nil; p->nxl = nxl; p->nsh = nsh; p->max_slices = max_slices;
     int rc = p3d_plan_create(&p->fft, device, nil, nxl, max_slices * nsh);
@@ -280,7 +265,7 @@ extern "C" int p3d_shearlet_plan_create(p3d_splan** out, int device, int nil, in
     p->stream = p3d::plan_stream(p->fft);
     auto bail = [&](const char* what, hipError_t e) {
         p3d_shearlet_plan_destroy(p);
-        return sfail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        return fail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     };
     hipError_t e;
 #define ALLOC(ptr, bytes) if ((e = hipMalloc((void**)&(ptr), (bytes))) != hipSuccess) return bail(#ptr, e)
@@ -335,10 +320,10 @@ extern "C" int p3d_shearlet_plan_create(p3d_splan** out, int device, int nil, in
 
 static int s_check(p3d_splan* p, int nslices, int dtype)
 {
-    if (!p) return sfail(P3D_ERR_INVALID, "NULL plan");
-    if (nslices < 1 || nslices > p->max_slices) return sfail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
-    if (dtype != P3D_C64 && dtype != P3D_F32) return sfail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    S_TRY(hipSetDevice(p->device));
+    if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
+    if (nslices < 1 || nslices > p->max_slices) return fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
+    if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    P3D_TRY(hipSetDevice(p->device));
     return P3D_OK;
 }
 
@@ -350,7 +335,7 @@ static int s_forward(p3d_splan* p, int ns, bool real_only, const int* done)
     spread_kernel<<<dim3(blocks_for(per, 1024), ns), 256, 0, p->stream>>>(p->F, p->psi, p->U, per, p->nsh, done);
     S_RC(p3d::fft2_async(p->fft, p->U, p->U, ns * p->nsh, 1));
     (void)real_only;
-    S_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -361,7 +346,7 @@ static int s_inverse(p3d_splan* p, int ns, const int* done)
     S_RC(p3d::fft2_async(p->fft, p->U, p->U, ns * p->nsh, 0));
     gather_kernel<<<dim3(blocks_for(per, 1024), ns), 256, 0, p->stream>>>(p->U, p->psi, p->F, per, p->nsh, done);
     S_RC(p3d::fft2_async(p->fft, p->F, p->F, ns, 1));
-    S_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -369,7 +354,7 @@ extern "C" {
 
 int p3d_shearlet_info(p3d_splan* p, double* row_group_fraction, int* paired)
 {
-    if (!p || !row_group_fraction) return sfail(P3D_ERR_INVALID, "NULL argument");
+    if (!p || !row_group_fraction) return fail(P3D_ERR_INVALID, "NULL argument");
     *row_group_fraction = p->sup ? p->sup_fraction : 1.0;
     if (paired) *paired = p->pair ? 1 : 0;
     return P3D_OK;
@@ -379,22 +364,22 @@ int p3d_shearlet_info(p3d_splan* p, double* row_group_fraction, int* paired)
 int p3d_shearlet_transform_c64(p3d_splan* p, const void* x, void* st, int nslices)
 {
     S_RC(s_check(p, nslices, P3D_C64));
-    if (!x || !st) return sfail(P3D_ERR_INVALID, "NULL buffer");
-    S_TRY(hipMemcpy(p->feed, x, sizeof(c32) * p->per() * nslices, hipMemcpyHostToDevice));
+    if (!x || !st) return fail(P3D_ERR_INVALID, "NULL buffer");
+    P3D_TRY(hipMemcpy(p->feed, x, sizeof(c32) * p->per() * nslices, hipMemcpyHostToDevice));
     S_RC(s_forward(p, nslices, false, nullptr));
-    S_TRY(hipStreamSynchronize(p->stream));
-    S_TRY(hipMemcpy(st, p->U, sizeof(c32) * p->per() * p->nsh * nslices, hipMemcpyDeviceToHost));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpy(st, p->U, sizeof(c32) * p->per() * p->nsh * nslices, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
 int p3d_shearlet_inverse_c64(p3d_splan* p, const void* st, void* x, int nslices)
 {
     S_RC(s_check(p, nslices, P3D_C64));
-    if (!x || !st) return sfail(P3D_ERR_INVALID, "NULL buffer");
-    S_TRY(hipMemcpy(p->U, st, sizeof(c32) * p->per() * p->nsh * nslices, hipMemcpyHostToDevice));
+    if (!x || !st) return fail(P3D_ERR_INVALID, "NULL buffer");
+    P3D_TRY(hipMemcpy(p->U, st, sizeof(c32) * p->per() * p->nsh * nslices, hipMemcpyHostToDevice));
     S_RC(s_inverse(p, nslices, nullptr));
-    S_TRY(hipStreamSynchronize(p->stream));
-    S_TRY(hipMemcpy(x, p->F, sizeof(c32) * p->per() * nslices, hipMemcpyDeviceToHost));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpy(x, p->F, sizeof(c32) * p->per() * nslices, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
@@ -403,19 +388,19 @@ int p3d_shearlet_inverse_c64(p3d_splan* p, const void* st, void* x, int nslices)
 int p3d_shearlet_stats(p3d_splan* p, const void* x, int dtype, int nslices, double* stats)
 {
     S_RC(s_check(p, nslices, dtype));
-    if (!x || !stats) return sfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
     const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
     // x: host or device pointer.  On the plan's stream: a device-to-device hipMemcpy runs on the null stream and need not have finished when it
     // returns, and the plan's stream does not wait for the null stream -- the kernels below would read st_x early (seen as wrong statistics
     // when several processes share the GPU)
-    S_TRY(hipMemcpyAsync(p->st_x, x, esz * p->per() * nslices, hipMemcpyDefault, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->st_x, x, esz * p->per() * nslices, hipMemcpyDefault, p->stream));
     if (p->sums_cap < (size_t)nslices) {
         if (p->sums) hipFree(p->sums);
         p->sums = nullptr; p->sums_cap = 0;
-        S_TRY(hipMalloc((void**)&p->sums, sizeof(double) * 2 * p->max_slices));
+        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * 2 * p->max_slices));
         p->sums_cap = 2 * (size_t)p->max_slices;
     }
-    S_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nslices, p->stream));
+    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nslices, p->stream));
     supdate_kernel<<<dim3(blocks_for(p->per(), 256), nslices), 256, 0, p->stream>>>(nullptr, p->feed, p->st_x, dtype, nullptr, nullptr, p->sums, 0, 0, 0, 1.0f,
                                                                                   p->per(), nullptr, 0);
     std::vector<float> host((size_t)nslices * p->nsh * 5);
@@ -428,9 +413,9 @@ int p3d_shearlet_stats(p3d_splan* p, const void* x, int dtype, int nslices, doub
     } else {
         S_RC(s_forward(p, nslices, dtype == P3D_F32, nullptr));
         sstats_kernel<<<nslices * p->nsh, 256, 0, p->stream>>>(p->U, p->per(), dtype == P3D_F32, p->stats);
-        S_TRY(hipGetLastError());
-        S_TRY(hipMemcpyAsync(host.data(), p->stats, sizeof(float) * host.size(), hipMemcpyDeviceToHost, p->stream));
-        S_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(hipGetLastError());
+        P3D_TRY(hipMemcpyAsync(host.data(), p->stats, sizeof(float) * host.size(), hipMemcpyDeviceToHost, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
     }
     for (size_t i = 0; i < host.size(); ++i) stats[i] = host[i];
     return P3D_OK;
@@ -441,10 +426,10 @@ int p3d_shearlet_run(p3d_splan* p, const void* x, int dtype, const float* mask, 
                      void* out, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms)
 {
     S_RC(s_check(p, nslices, dtype));
-    if (!x || !mask || !tau || !prm || !out) return sfail(P3D_ERR_INVALID, "NULL argument");
-    if (prm->niter < 1) return sfail(P3D_ERR_INVALID, "niter must be >= 1");
+    if (!x || !mask || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
     if (prm->thresh_op < P3D_OP_HARD || prm->thresh_op > P3D_OP_GARROTE)
-        return sfail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the shearlet transform", prm->thresh_op);
+        return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the shearlet transform", prm->thresh_op);
     const int niter = prm->niter, nsh = p->nsh;
     const bool early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE, real_only = dtype == P3D_F32;
     const size_t per = p->per(), esz = real_only ? sizeof(float) : sizeof(c32);
@@ -452,28 +437,28 @@ int p3d_shearlet_run(p3d_splan* p, const void* x, int dtype, const float* mask, 
     if (p->tau_cap < ntau) {
         if (p->tau) hipFree(p->tau);
         p->tau = nullptr; p->tau_cap = 0;
-        S_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * ntau));
+        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * ntau));
         p->tau_cap = ntau;
     }
     if (p->sums_cap < nsum) {
         if (p->sums) hipFree(p->sums);
         p->sums = nullptr; p->sums_cap = 0;
-        S_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
+        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
         p->sums_cap = nsum;
     }
     std::vector<c32> tau_f(ntau);
     for (size_t i = 0; i < ntau; ++i) {
         tau_f[i] = p3d::tau_for_device(tau[2 * i], tau[2 * i + 1], prm->thresh_op == P3D_OP_HARD);
-        if (real_only && tau[2 * i + 1] != 0.0) return sfail(P3D_ERR_INVALID, "complex thresholds need a complex64 cube");
+        if (real_only && tau[2 * i + 1] != 0.0) return fail(P3D_ERR_INVALID, "complex thresholds need a complex64 cube");
     }
     std::vector<int> done_h(nslices, 0);
     if (active) for (int s = 0; s < nslices; ++s) done_h[s] = active[s] ? 0 : -1;
-    S_TRY(hipMemcpyAsync(p->st_x, x, esz * per * nslices, hipMemcpyDefault, p->stream));   // x, mask, out: host or device pointers (on the plan's stream, see p3d_shearlet_stats)
-    S_TRY(hipMemcpyAsync(p->mask, mask, sizeof(float) * per, hipMemcpyDefault, p->stream));
-    S_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
-    S_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    S_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    S_TRY(hipEventRecord(p->ev0, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->st_x, x, esz * per * nslices, hipMemcpyDefault, p->stream));   // x, mask, out: host or device pointers (on the plan's stream, see p3d_shearlet_stats)
+    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(float) * per, hipMemcpyDefault, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
+    P3D_TRY(hipEventRecord(p->ev0, p->stream));
     const dim3 ugrid(blocks_for(per, 256), nslices);
     supdate_kernel<<<ugrid, 256, 0, p->stream>>>(nullptr, p->feed, p->st_x, dtype, p->mask, p->st_out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, per,
                                                 p->done, 0);
@@ -499,17 +484,17 @@ int p3d_shearlet_run(p3d_splan* p, const void* x, int dtype, const float* mask, 
                                                     (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0, (float)prm->alpha, per, p->done, last ? 1 : 0);
         if (early) sconv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
     }
-    S_TRY(hipGetLastError());
-    S_TRY(hipEventRecord(p->ev1, p->stream));
-    S_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) S_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-    S_TRY(hipStreamSynchronize(p->stream));
-    S_TRY(hipMemcpyAsync(out, p->st_out, esz * per * nslices, hipMemcpyDefault, p->stream));
-    S_TRY(hipStreamSynchronize(p->stream));   // (the caller may read `out` on any stream once this returns)
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipEventRecord(p->ev1, p->stream));
+    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
+    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpyAsync(out, p->st_out, esz * per * nslices, hipMemcpyDefault, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));   // (the caller may read `out` on any stream once this returns)
     if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
     if (elapsed_ms) {
         float ms = 0.f;
-        S_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
         *elapsed_ms = ms;
     }
     return P3D_OK;

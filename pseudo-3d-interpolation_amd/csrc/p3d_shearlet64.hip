@@ -21,13 +21,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "p3d.h"
+#include "p3d_host.hpp"
 #include "p3d_internal.hpp"
+
+using p3d::fail;
 
 namespace {
 
@@ -35,21 +36,6 @@ struct __attribute__((aligned(16))) c64 {
     double x, y;
 };
 
-int s64fail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define S_TRY(expr)                                                                                       \
-    do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) return s64fail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 #define S_RC(expr)           \
     do {                     \
         int rc_ = (expr);    \
@@ -342,10 +328,10 @@ bool real_dtype(int dtype) { return dtype == P3D_F64 || dtype == P3D_F32; }
 
 int s_check(p3d_splan64* p, int nslices, int dtype)
 {
-    if (!p) return s64fail(P3D_ERR_INVALID, "NULL plan");
-    if (nslices < 1 || nslices > p->max_slices) return s64fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
-    if (dtype != P3D_C64 && dtype != P3D_F32 && dtype != P3D_C128 && dtype != P3D_F64) return s64fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    S_TRY(hipSetDevice(p->device));
+    if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
+    if (nslices < 1 || nslices > p->max_slices) return fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
+    if (dtype != P3D_C64 && dtype != P3D_F32 && dtype != P3D_C128 && dtype != P3D_F64) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    P3D_TRY(hipSetDevice(p->device));
     return P3D_OK;
 }
 
@@ -354,7 +340,7 @@ int ensure_sums(p3d_splan64* p, size_t n)
     if (p->sums_cap < n) {
         if (p->sums) hipFree(p->sums);
         p->sums = nullptr; p->sums_cap = 0;
-        S_TRY(hipMalloc((void**)&p->sums, sizeof(double) * n));
+        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * n));
         p->sums_cap = n;
     }
     return P3D_OK;
@@ -366,7 +352,7 @@ int take_x(p3d_splan64* p, const void* x, int dtype, int nslices)
     if (on_plan_device(p, x)) {
         p->cur_x = x;
     } else {
-        S_TRY(hipMemcpyAsync(p->st_x, x, elem_bytes(dtype) * p->per() * nslices, hipMemcpyDefault, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->st_x, x, elem_bytes(dtype) * p->per() * nslices, hipMemcpyDefault, p->stream));
         p->cur_x = p->st_x;
     }
     return P3D_OK;
@@ -379,7 +365,7 @@ int s_forward(p3d_splan64* p, int ns, const int* done)
     S_RC(p3d::plan64_fft2(p->fft, p->F, ns, false, done, 1));
     spread64_kernel<<<dim3(blocks_for(per, 1024), ns), 256, 0, p->stream>>>(p->F, p->psi, p->U, per, p->nsh, done);
     S_RC(p3d::plan64_fft2(p->fft, p->U, ns * p->nsh, true, done, p->nsh));
-    S_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -390,7 +376,7 @@ int s_inverse(p3d_splan64* p, int ns, const int* done)
     S_RC(p3d::plan64_fft2(p->fft, p->U, ns * p->nsh, false, done, p->nsh));
     gather64_kernel<<<dim3(blocks_for(per, 1024), ns), 256, 0, p->stream>>>(p->U, p->psi, p->F, per, p->nsh, done);
     S_RC(p3d::plan64_fft2(p->fft, p->F, ns, true, done, 1));
-    S_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -423,10 +409,10 @@ int p3d_shearlet64_plan_destroy(p3d_splan64* p)
 // psi: HOST double [nsh][nil][nxl] (real spectra, FFT order)
 int p3d_shearlet64_plan_create(p3d_splan64** out, int device, int nil, int nxl, int nsh, const double* psi, int max_slices)
 {
-    if (!out || !psi) return s64fail(P3D_ERR_INVALID, "NULL argument");
+    if (!out || !psi) return fail(P3D_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    if (nil < 1 || nxl < 1 || nsh < 1 || max_slices < 1) return s64fail(P3D_ERR_INVALID, "bad shape / batch size");
-    if ((long long)max_slices * nsh > 65535) return s64fail(P3D_ERR_INVALID, "max_slices * nsh = %lld exceeds 65535", (long long)max_slices * nsh);
+    if (nil < 1 || nxl < 1 || nsh < 1 || max_slices < 1) return fail(P3D_ERR_INVALID, "bad shape / batch size");
+    if ((long long)max_slices * nsh > 65535) return fail(P3D_ERR_INVALID, "max_slices * nsh = %lld exceeds 65535", (long long)max_slices * nsh);
     p3d_splan64* p = new p3d_splan64;
     p->device = device; p->nil = nil; p->nxl = nxl; p->nsh = nsh; p->max_slices = max_slices;
     int rc = p3d_plan64_create(&p->pf, device, nil, nxl, max_slices);
@@ -444,7 +430,7 @@ int p3d_shearlet64_plan_create(p3d_splan64** out, int device, int nil, int nxl, 
     }
     auto bail = [&](const char* what, hipError_t e) {
         p3d_shearlet64_plan_destroy(p);
-        return s64fail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        return fail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     };
     hipError_t e;
 #define ALLOC(ptr, bytes) if ((e = hipMalloc((void**)&(ptr), (bytes))) != hipSuccess) return bail(#ptr, e)
@@ -514,7 +500,7 @@ int p3d_shearlet64_fused_shape(int nil, int nxl)
 
 int p3d_shearlet64_info(p3d_splan64* p, int* fused, double* row_group_fraction)
 {
-    if (!p || !fused) return s64fail(P3D_ERR_INVALID, "NULL argument");
+    if (!p || !fused) return fail(P3D_ERR_INVALID, "NULL argument");
     *fused = p->pf ? (p->pair ? 3 : 1) : 0;   // bit 1: real cubes take the Hermitian form (two columns per transform)
     if (row_group_fraction) *row_group_fraction = p->sup ? p->sup_fraction : 1.0;
     return P3D_OK;
@@ -526,7 +512,7 @@ int p3d_shearlet64_info(p3d_splan64* p, int* fused, double* row_group_fraction)
 int p3d_shearlet64_stats(p3d_splan64* p, const void* x, int dtype, int nslices, double* stats)
 {
     S_RC(s_check(p, nslices, dtype));
-    if (!x || !stats) return s64fail(P3D_ERR_INVALID, "NULL buffer");
+    if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
     S_RC(take_x(p, x, dtype, nslices));
     if (p->pf) {
         S_RC(ensure_sums(p, (size_t)nslices));
@@ -540,9 +526,9 @@ int p3d_shearlet64_stats(p3d_splan64* p, const void* x, int dtype, int nslices, 
         S_RC(s_forward(p, nslices, nullptr));
     }
     sstats64_kernel<<<nslices * p->nsh, 256, 0, p->stream>>>(p->U, p->per(), real_dtype(dtype) ? 1 : 0, p->stats);
-    S_TRY(hipGetLastError());
-    S_TRY(hipMemcpyAsync(stats, p->stats, sizeof(double) * 5 * (size_t)nslices * p->nsh, hipMemcpyDeviceToHost, p->stream));
-    S_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipMemcpyAsync(stats, p->stats, sizeof(double) * 5 * (size_t)nslices * p->nsh, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     return P3D_OK;
 }
 
@@ -552,21 +538,21 @@ int p3d_shearlet64_run(p3d_splan64* p, const void* x, int dtype, const double* m
                        void* out, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms)
 {
     S_RC(s_check(p, nslices, dtype));
-    if (!x || !mask || !tau || !prm || !out) return s64fail(P3D_ERR_INVALID, "NULL argument");
-    if (prm->niter < 1) return s64fail(P3D_ERR_INVALID, "niter must be >= 1");
+    if (!x || !mask || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
     if (prm->thresh_op < P3D_OP_HARD || prm->thresh_op > P3D_OP_GARROTE)
-        return s64fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the shearlet transform", prm->thresh_op);
+        return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the shearlet transform", prm->thresh_op);
     const int niter = prm->niter, nsh = p->nsh;
     const bool early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE, real_only = real_dtype(dtype);
     const size_t per = p->per();
     const size_t ntau = (size_t)nslices * niter * nsh, nsum = (size_t)(niter + 1) * nslices;
     if (real_only)
         for (size_t i = 0; i < ntau; ++i)
-            if (tau[2 * i + 1] != 0.0) return s64fail(P3D_ERR_INVALID, "complex thresholds need a complex cube");
+            if (tau[2 * i + 1] != 0.0) return fail(P3D_ERR_INVALID, "complex thresholds need a complex cube");
     if (p->tau_cap < ntau) {
         if (p->tau) hipFree(p->tau);
         p->tau = nullptr; p->tau_cap = 0;
-        S_TRY(hipMalloc((void**)&p->tau, sizeof(c64) * ntau));
+        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c64) * ntau));
         p->tau_cap = ntau;
     }
     S_RC(ensure_sums(p, nsum));
@@ -575,11 +561,11 @@ int p3d_shearlet64_run(p3d_splan64* p, const void* x, int dtype, const double* m
     S_RC(take_x(p, x, dtype, nslices));
     const bool direct_out = on_plan_device(p, out);
     p->cur_out = direct_out ? out : p->st_out;
-    S_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * per, hipMemcpyDefault, p->stream));
-    S_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));
-    S_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    S_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    S_TRY(hipEventRecord(p->ev0, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * per, hipMemcpyDefault, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
+    P3D_TRY(hipEventRecord(p->ev0, p->stream));
     if (p->pf) {
         const double scale = 1.0 / ((double)p->nil * p->nxl);
         const int pair = (p->pair && real_only) ? 1 : 0, rows = pair ? p->nil / 2 + 1 : 0;
@@ -613,16 +599,16 @@ int p3d_shearlet64_run(p3d_splan64* p, const void* x, int dtype, const double* m
             if (early) sconv64_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
         }
     }
-    S_TRY(hipGetLastError());
-    S_TRY(hipEventRecord(p->ev1, p->stream));
-    S_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) S_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-    if (!direct_out) S_TRY(hipMemcpyAsync(out, p->st_out, elem_bytes(dtype) * per * nslices, hipMemcpyDefault, p->stream));
-    S_TRY(hipStreamSynchronize(p->stream));   // (the caller may read `out` on any stream once this returns)
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipEventRecord(p->ev1, p->stream));
+    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
+    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+    if (!direct_out) P3D_TRY(hipMemcpyAsync(out, p->st_out, elem_bytes(dtype) * per * nslices, hipMemcpyDefault, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));   // (the caller may read `out` on any stream once this returns)
     if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
     if (elapsed_ms) {
         float ms = 0.f;
-        S_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
         *elapsed_ms = ms;
     }
     return P3D_OK;

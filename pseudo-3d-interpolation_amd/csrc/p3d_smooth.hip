@@ -7,35 +7,16 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <vector>
 
 #include "p3d.h"
-#include "p3d_internal.hpp"
+#include "p3d_host.hpp"
+
+using p3d::DevBuf;
+using p3d::fail;
+using p3d::use_device;
 
 namespace {
-
-int mfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define M_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return mfail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
 
 // 'reflect' of scipy.ndimage: index i of an axis of n samples, any integer
 __device__ __forceinline__ int reflect(int i, int n)
@@ -93,13 +74,9 @@ unsigned blocks_for(size_t n) { const size_t b = (n + 255) / 256; return (unsign
 
 int check(int device, const float* x, float* out, size_t nslices, int ny, int nx)
 {
-    if (!x || !out) return mfail(P3D_ERR_INVALID, "NULL buffer");
-    if (nslices < 1 || ny < 1 || nx < 1) return mfail(P3D_ERR_INVALID, "bad shape");
-    int ndev = 0;
-    M_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return mfail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    M_TRY(hipSetDevice(device));
-    return P3D_OK;
+    if (!x || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (nslices < 1 || ny < 1 || nx < 1) return fail(P3D_ERR_INVALID, "bad shape");
+    return use_device(device);
 }
 
 }  // namespace
@@ -110,9 +87,9 @@ int p3d_smooth_gaussian(int device, const float* x, size_t nslices, int ny, int 
 {
     int rc = check(device, x, out, nslices, ny, nx);
     if (rc) return rc;
-    if (!(sigma > 0.0) || !(truncate > 0.0)) return mfail(P3D_ERR_INVALID, "sigma and truncate must be positive");
+    if (!(sigma > 0.0) || !(truncate > 0.0)) return fail(P3D_ERR_INVALID, "sigma and truncate must be positive");
     const int r = (int)(truncate * sigma + 0.5);
-    if (r > 4096) return mfail(P3D_ERR_UNSUPPORTED, "kernel radius %d: up to 4096 samples", r);
+    if (r > 4096) return fail(P3D_ERR_UNSUPPORTED, "kernel radius %d: up to 4096 samples", r);
     std::vector<double> wd(2 * r + 1);
     double sum = 0.0;
     for (int j = -r; j <= r; ++j) sum += wd[j + r] = std::exp(-0.5 * (double)j * j / (sigma * sigma));
@@ -120,16 +97,16 @@ int p3d_smooth_gaussian(int device, const float* x, size_t nslices, int ny, int 
     for (int j = 0; j <= 2 * r; ++j) w[j] = (float)(wd[j] / sum);
     const size_t total = nslices * (size_t)ny * nx;
     DevBuf a, b, dw;
-    M_TRY(hipMalloc(&a.p, sizeof(float) * total));
-    M_TRY(hipMalloc(&b.p, sizeof(float) * total));
-    M_TRY(hipMalloc(&dw.p, sizeof(float) * w.size()));
-    M_TRY(hipMemcpy(a.p, x, sizeof(float) * total, hipMemcpyHostToDevice));
-    M_TRY(hipMemcpy(dw.p, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&a.p, sizeof(float) * total));
+    P3D_TRY(hipMalloc(&b.p, sizeof(float) * total));
+    P3D_TRY(hipMalloc(&dw.p, sizeof(float) * w.size()));
+    P3D_TRY(hipMemcpy(a.p, x, sizeof(float) * total, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(dw.p, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice));
     gauss_axis_kernel<<<blocks_for(total), 256>>>((const float*)a.p, (float*)b.p, (const float*)dw.p, r, ny, nx, 0, total);
     gauss_axis_kernel<<<blocks_for(total), 256>>>((const float*)b.p, (float*)a.p, (const float*)dw.p, r, ny, nx, 1, total);
-    M_TRY(hipGetLastError());
-    M_TRY(hipDeviceSynchronize());
-    M_TRY(hipMemcpy(out, a.p, sizeof(float) * total, hipMemcpyDeviceToHost));
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipMemcpy(out, a.p, sizeof(float) * total, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
@@ -137,18 +114,18 @@ int p3d_smooth_median(int device, const float* x, size_t nslices, int ny, int nx
 {
     int rc = check(device, x, out, nslices, ny, nx);
     if (rc) return rc;
-    if (size != 3 && size != 5 && size != 7) return mfail(P3D_ERR_UNSUPPORTED, "median window %d: 3, 5 and 7 are implemented", size);
+    if (size != 3 && size != 5 && size != 7) return fail(P3D_ERR_UNSUPPORTED, "median window %d: 3, 5 and 7 are implemented", size);
     const size_t total = nslices * (size_t)ny * nx;
     DevBuf a, b;
-    M_TRY(hipMalloc(&a.p, sizeof(float) * total));
-    M_TRY(hipMalloc(&b.p, sizeof(float) * total));
-    M_TRY(hipMemcpy(a.p, x, sizeof(float) * total, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&a.p, sizeof(float) * total));
+    P3D_TRY(hipMalloc(&b.p, sizeof(float) * total));
+    P3D_TRY(hipMemcpy(a.p, x, sizeof(float) * total, hipMemcpyHostToDevice));
     if (size == 3) median_kernel<3><<<blocks_for(total), 256>>>((const float*)a.p, (float*)b.p, ny, nx, total);
     else if (size == 5) median_kernel<5><<<blocks_for(total), 256>>>((const float*)a.p, (float*)b.p, ny, nx, total);
     else median_kernel<7><<<blocks_for(total), 256>>>((const float*)a.p, (float*)b.p, ny, nx, total);
-    M_TRY(hipGetLastError());
-    M_TRY(hipDeviceSynchronize());
-    M_TRY(hipMemcpy(out, b.p, sizeof(float) * total, hipMemcpyDeviceToHost));
+    P3D_TRY(hipGetLastError());
+    P3D_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipMemcpy(out, b.p, sizeof(float) * total, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 

@@ -22,35 +22,16 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <vector>
 
 #include "p3d.h"
-#include "p3d_internal.hpp"
+#include "p3d_host.hpp"
+
+using p3d::DevBuf;
+using p3d::fail;
+using p3d::use_device;
 
 namespace {
-
-int sfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define S_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return sfail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
 
 constexpr int WAVE = 64;
 constexpr int CHUNK = 4 * WAVE;                 // samples per step of a wave
@@ -307,24 +288,15 @@ __global__ void __launch_bounds__(SHIFT_BS) static_shift_kernel(const float* __r
     }
 }
 
-int set_device(int device)
-{
-    int ndev = 0;
-    S_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return sfail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    S_TRY(hipSetDevice(device));
-    return P3D_OK;
-}
-
 int check_section(int ntr, int ns)
 {
-    if (ntr < 1 || ns < 1) return sfail(P3D_ERR_INVALID, "bad section shape (%d traces, %d samples)", ntr, ns);
+    if (ntr < 1 || ns < 1) return fail(P3D_ERR_INVALID, "bad section shape (%d traces, %d samples)", ntr, ns);
     return P3D_OK;
 }
 
 int check_slice(int ns, int padded, int nvalid)
 {
-    if (padded && (nvalid < 1 || nvalid > ns)) return sfail(P3D_ERR_INVALID, "%d valid samples do not fit traces of %d samples", nvalid, ns);
+    if (padded && (nvalid < 1 || nvalid > ns)) return fail(P3D_ERR_INVALID, "%d valid samples do not fit traces of %d samples", nvalid, ns);
     return P3D_OK;
 }
 
@@ -332,9 +304,9 @@ int check_stalta(int ntr, int ns, int padded, int nvalid, int nsta, int nlta)
 {
     if (int rc = check_section(ntr, ns)) return rc;
     if (int rc = check_slice(ns, padded, nvalid)) return rc;
-    if (nsta < 1 || nlta < 1) return sfail(P3D_ERR_INVALID, "the STA / LTA windows must be at least 1 sample long (nsta %d, nlta %d)", nsta, nlta);
-    if (nsta > nlta) return sfail(P3D_ERR_INVALID, "the short window (%d samples) is longer than the long one (%d)", nsta, nlta);
-    if (nlta > MAXNLTA) return sfail(P3D_ERR_UNSUPPORTED, "long windows of up to %d samples are supported, got %d", MAXNLTA, nlta);
+    if (nsta < 1 || nlta < 1) return fail(P3D_ERR_INVALID, "the STA / LTA windows must be at least 1 sample long (nsta %d, nlta %d)", nsta, nlta);
+    if (nsta > nlta) return fail(P3D_ERR_INVALID, "the short window (%d samples) is longer than the long one (%d)", nsta, nlta);
+    if (nlta > MAXNLTA) return fail(P3D_ERR_UNSUPPORTED, "long windows of up to %d samples are supported, got %d", MAXNLTA, nlta);
     return P3D_OK;
 }
 
@@ -342,10 +314,10 @@ int check_peak(int ntr, int ns, int padded, int nvalid, int win, int n)
 {
     if (int rc = check_section(ntr, ns)) return rc;
     if (int rc = check_slice(ns, padded, nvalid)) return rc;
-    if (win < 1) return sfail(P3D_ERR_INVALID, "the search window must reach at least 1 sample to either side, got %d", win);
-    if (win > MAXWIN) return sfail(P3D_ERR_UNSUPPORTED, "search windows of up to +- %d samples are supported, got %d", MAXWIN, win);
-    if (n < 1) return sfail(P3D_ERR_INVALID, "at least 1 amplitude must be selected, got %d", n);
-    if (n > 2 * win + 1) return sfail(P3D_ERR_UNSUPPORTED, "a window of %d samples cannot give %d amplitudes", 2 * win + 1, n);
+    if (win < 1) return fail(P3D_ERR_INVALID, "the search window must reach at least 1 sample to either side, got %d", win);
+    if (win > MAXWIN) return fail(P3D_ERR_UNSUPPORTED, "search windows of up to +- %d samples are supported, got %d", MAXWIN, win);
+    if (n < 1) return fail(P3D_ERR_INVALID, "at least 1 amplitude must be selected, got %d", n);
+    if (n > 2 * win + 1) return fail(P3D_ERR_UNSUPPORTED, "a window of %d samples cannot give %d amplitudes", 2 * win + 1, n);
     return P3D_OK;
 }
 
@@ -358,44 +330,44 @@ int ring_size(int nlta)
 
 int scan_dev(const float* a, int ntr, int ns, int* first)
 {
-    if (!a || !first) return sfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!a || !first) return fail(P3D_ERR_INVALID, "NULL buffer");
     static_scan_kernel<<<(unsigned)ntr, WAVE, 0, 0>>>(a, ns, (long long)ntr * ns, first);
-    S_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
 int stalta_dev(int pass, const float* a, int ntr, int ns, const int* first, int padded, int nvalid, int nsta, int nlta, double thr, double* peak, int* cross)
 {
-    if (!a || !first || (pass == 0 ? !peak : !cross)) return sfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!a || !first || (pass == 0 ? !peak : !cross)) return fail(P3D_ERR_INVALID, "NULL buffer");
     const int r = ring_size(nlta);
     const size_t lds = (size_t)r * sizeof(double);
     const long long total = (long long)ntr * ns;
     if (pass == 0) static_stalta_kernel<0><<<(unsigned)ntr, WAVE, lds, 0>>>(a, ns, total, first, padded, nvalid, nsta, nlta, r - 1, thr, peak, cross);
     else static_stalta_kernel<1><<<(unsigned)ntr, WAVE, lds, 0>>>(a, ns, total, first, padded, nvalid, nsta, nlta, r - 1, thr, peak, cross);
-    S_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
 int peak_dev(const float* a, int ntr, int ns, const int* first, int padded, int nvalid, const int* base, int win, int n, int* out)
 {
-    if (!a || !first || !base || !out) return sfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!a || !first || !base || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
     const int L = 2 * win + 1;
     if (L <= 64) static_peak_kernel<1><<<(unsigned)ntr, WAVE, 0, 0>>>(a, ns, first, padded, nvalid, base, win, n, out);
     else if (L <= 128) static_peak_kernel<2><<<(unsigned)ntr, WAVE, 0, 0>>>(a, ns, first, padded, nvalid, base, win, n, out);
     else if (L <= 256) static_peak_kernel<4><<<(unsigned)ntr, WAVE, 0, 0>>>(a, ns, first, padded, nvalid, base, win, n, out);
     else static_peak_kernel<8><<<(unsigned)ntr, WAVE, 0, 0>>>(a, ns, first, padded, nvalid, base, win, n, out);
-    S_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
 int shift_dev(const float* in, int ntr, int ns, const int* shift, float* out)
 {
-    if (!in || !shift || !out) return sfail(P3D_ERR_INVALID, "NULL buffer");
-    if (in == out) return sfail(P3D_ERR_INVALID, "the shift needs separate input and output buffers");
+    if (!in || !shift || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (in == out) return fail(P3D_ERR_INVALID, "the shift needs separate input and output buffers");
     const long long total = (long long)ntr * ns, quads = (total + 3) / 4, blocks = (quads + SHIFT_BS - 1) / SHIFT_BS;
-    if (blocks > 0x7fffffffll) return sfail(P3D_ERR_UNSUPPORTED, "section too large for one launch (%lld workgroups)", blocks);
+    if (blocks > 0x7fffffffll) return fail(P3D_ERR_UNSUPPORTED, "section too large for one launch (%lld workgroups)", blocks);
     static_shift_kernel<<<(unsigned)blocks, SHIFT_BS, 0, 0>>>(in, shift, ns, total, out);
-    S_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -406,9 +378,9 @@ extern "C" {
 int p3d_static_scan_dev(int device, const float* section_dev, int ntr, int ns, int* first_dev)
 {
     if (int rc = check_section(ntr, ns)) return rc;
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (int rc = scan_dev(section_dev, ntr, ns, first_dev)) return rc;
-    S_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
@@ -416,9 +388,9 @@ int p3d_static_stalta_max_dev(int device, const float* section_dev, int ntr, int
                               double* peak_dev)
 {
     if (int rc = check_stalta(ntr, ns, padded, nvalid, nsta, nlta)) return rc;
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (int rc = stalta_dev(0, section_dev, ntr, ns, first_dev, padded, nvalid, nsta, nlta, 0.0, peak_dev, nullptr)) return rc;
-    S_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
@@ -426,9 +398,9 @@ int p3d_static_stalta_cross_dev(int device, const float* section_dev, int ntr, i
                                 double threshold, int* cross_dev)
 {
     if (int rc = check_stalta(ntr, ns, padded, nvalid, nsta, nlta)) return rc;
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (int rc = stalta_dev(1, section_dev, ntr, ns, first_dev, padded, nvalid, nsta, nlta, threshold, nullptr, cross_dev)) return rc;
-    S_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
@@ -436,18 +408,18 @@ int p3d_static_peak_dev(int device, const float* section_dev, int ntr, int ns, c
                         int n, int* peak_idx_dev)
 {
     if (int rc = check_peak(ntr, ns, padded, nvalid, win, n)) return rc;
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (int rc = peak_dev(section_dev, ntr, ns, first_dev, padded, nvalid, base_dev, win, n, peak_idx_dev)) return rc;
-    S_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
 int p3d_static_shift_dev(int device, const float* in_dev, int ntr, int ns, const int* shift_on_dev, float* out_dev)
 {
     if (int rc = check_section(ntr, ns)) return rc;
-    if (int rc = set_device(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (int rc = shift_dev(in_dev, ntr, ns, shift_on_dev, out_dev)) return rc;
-    S_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 
@@ -455,28 +427,28 @@ int p3d_static_detect(int device, const float* section, int ntr, int ns, int pad
                       int* cross)
 {
     if (int rc = check_stalta(ntr, ns, padded, nvalid, nsta, nlta)) return rc;
-    if (!section || !threshold || !first || !cross) return sfail(P3D_ERR_INVALID, "NULL buffer");
-    if (int rc = set_device(device)) return rc;
+    if (!section || !threshold || !first || !cross) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (int rc = use_device(device)) return rc;
     const size_t nsec = (size_t)ntr * ns * sizeof(float);
     DevBuf da, df, dp, dc;
-    S_TRY(hipMalloc(&da.p, nsec));
-    S_TRY(hipMalloc(&df.p, (size_t)ntr * sizeof(int)));
-    S_TRY(hipMalloc(&dp.p, (size_t)ntr * sizeof(double)));
-    S_TRY(hipMalloc(&dc.p, (size_t)ntr * sizeof(int)));
-    S_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&da.p, nsec));
+    P3D_TRY(hipMalloc(&df.p, (size_t)ntr * sizeof(int)));
+    P3D_TRY(hipMalloc(&dp.p, (size_t)ntr * sizeof(double)));
+    P3D_TRY(hipMalloc(&dc.p, (size_t)ntr * sizeof(int)));
+    P3D_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
     if (int rc = scan_dev((const float*)da.p, ntr, ns, (int*)df.p)) return rc;
-    S_TRY(hipMemcpy(first, df.p, (size_t)ntr * sizeof(int), hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(first, df.p, (size_t)ntr * sizeof(int), hipMemcpyDeviceToHost));
     if (std::isnan(*threshold)) {   // the reference's default: the largest ratio of rows nlta ... 2 nlta - 1 over the live traces
         std::vector<double> peak(ntr);
         if (int rc = stalta_dev(0, (const float*)da.p, ntr, ns, (const int*)df.p, padded, nvalid, nsta, nlta, 0.0, (double*)dp.p, nullptr)) return rc;
-        S_TRY(hipMemcpy(peak.data(), dp.p, (size_t)ntr * sizeof(double), hipMemcpyDeviceToHost));
+        P3D_TRY(hipMemcpy(peak.data(), dp.p, (size_t)ntr * sizeof(double), hipMemcpyDeviceToHost));
         double thr = 0.0;
         for (int x = 0; x < ntr; ++x)
             if (first[x] >= 0) thr = std::max(thr, peak[x]);
         *threshold = thr;
     }
     if (int rc = stalta_dev(1, (const float*)da.p, ntr, ns, (const int*)df.p, padded, nvalid, nsta, nlta, *threshold, nullptr, (int*)dc.p)) return rc;
-    S_TRY(hipMemcpy(cross, dc.p, (size_t)ntr * sizeof(int), hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(cross, dc.p, (size_t)ntr * sizeof(int), hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
@@ -484,36 +456,36 @@ int p3d_static_peak(int device, const float* section, int ntr, int ns, const int
                     int* peak_idx)
 {
     if (int rc = check_peak(ntr, ns, padded, nvalid, win, n)) return rc;
-    if (!section || !first || !base || !peak_idx) return sfail(P3D_ERR_INVALID, "NULL buffer");
-    if (int rc = set_device(device)) return rc;
+    if (!section || !first || !base || !peak_idx) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (int rc = use_device(device)) return rc;
     const size_t nsec = (size_t)ntr * ns * sizeof(float), nint = (size_t)ntr * sizeof(int);
     DevBuf da, df, db, dout;
-    S_TRY(hipMalloc(&da.p, nsec));
-    S_TRY(hipMalloc(&df.p, nint));
-    S_TRY(hipMalloc(&db.p, nint));
-    S_TRY(hipMalloc(&dout.p, nint));
-    S_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
-    S_TRY(hipMemcpy(df.p, first, nint, hipMemcpyHostToDevice));
-    S_TRY(hipMemcpy(db.p, base, nint, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&da.p, nsec));
+    P3D_TRY(hipMalloc(&df.p, nint));
+    P3D_TRY(hipMalloc(&db.p, nint));
+    P3D_TRY(hipMalloc(&dout.p, nint));
+    P3D_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(df.p, first, nint, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(db.p, base, nint, hipMemcpyHostToDevice));
     if (int rc = peak_dev((const float*)da.p, ntr, ns, (const int*)df.p, padded, nvalid, (const int*)db.p, win, n, (int*)dout.p)) return rc;
-    S_TRY(hipMemcpy(peak_idx, dout.p, nint, hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(peak_idx, dout.p, nint, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
 int p3d_static_shift(int device, const float* section, int ntr, int ns, const int* shift, float* out)
 {
     if (int rc = check_section(ntr, ns)) return rc;
-    if (!section || !shift || !out) return sfail(P3D_ERR_INVALID, "NULL buffer");
-    if (int rc = set_device(device)) return rc;
+    if (!section || !shift || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (int rc = use_device(device)) return rc;
     const size_t nsec = (size_t)ntr * ns * sizeof(float), nint = (size_t)ntr * sizeof(int);
     DevBuf da, ds, dout;
-    S_TRY(hipMalloc(&da.p, nsec));
-    S_TRY(hipMalloc(&ds.p, nint));
-    S_TRY(hipMalloc(&dout.p, nsec));
-    S_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
-    S_TRY(hipMemcpy(ds.p, shift, nint, hipMemcpyHostToDevice));
+    P3D_TRY(hipMalloc(&da.p, nsec));
+    P3D_TRY(hipMalloc(&ds.p, nint));
+    P3D_TRY(hipMalloc(&dout.p, nsec));
+    P3D_TRY(hipMemcpy(da.p, section, nsec, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(ds.p, shift, nint, hipMemcpyHostToDevice));
     if (int rc = shift_dev((const float*)da.p, ntr, ns, (const int*)ds.p, (float*)dout.p)) return rc;
-    S_TRY(hipMemcpy(out, dout.p, nsec, hipMemcpyDeviceToHost));
+    P3D_TRY(hipMemcpy(out, dout.p, nsec, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 

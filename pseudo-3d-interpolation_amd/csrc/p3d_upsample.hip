@@ -7,34 +7,14 @@
 // One thread per output sample, 64-bit indices; slices [nslices][ny][nx] row-major.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
 #include "p3d.h"
-#include "p3d_internal.hpp"
+#include "p3d_host.hpp"
+
+using p3d::DevBuf;
+using p3d::fail;
+using p3d::use_device;
 
 namespace {
-
-int ufail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define U_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return ufail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-};
 
 // C = 1: float32, C = 2: complex64 as interleaved float pairs
 template <int C>
@@ -69,11 +49,11 @@ __global__ void __launch_bounds__(256) upsample_kernel(const float* __restrict__
 
 int check_table(const int* idx, const float* w, int n_out, int n_in, const char* axis)
 {
-    if (!idx || !w || n_out < 1) return ufail(P3D_ERR_INVALID, "%s: empty or NULL interpolation table", axis);
+    if (!idx || !w || n_out < 1) return fail(P3D_ERR_INVALID, "%s: empty or NULL interpolation table", axis);
     for (int o = 0; o < n_out; ++o) {
-        if (idx[o] < 0 || idx[o] >= n_in) return ufail(P3D_ERR_INVALID, "%s: source line %d of output line %d outside 0 .. %d", axis, idx[o], o, n_in - 1);
-        if (!(w[o] >= 0.0f && w[o] < 1.0f)) return ufail(P3D_ERR_INVALID, "%s: weight %g of output line %d outside [0, 1)", axis, (double)w[o], o);
-        if (w[o] != 0.0f && idx[o] + 1 >= n_in) return ufail(P3D_ERR_INVALID, "%s: output line %d interpolates past the last source line", axis, o);
+        if (idx[o] < 0 || idx[o] >= n_in) return fail(P3D_ERR_INVALID, "%s: source line %d of output line %d outside 0 .. %d", axis, idx[o], o, n_in - 1);
+        if (!(w[o] >= 0.0f && w[o] < 1.0f)) return fail(P3D_ERR_INVALID, "%s: weight %g of output line %d outside [0, 1)", axis, (double)w[o], o);
+        if (w[o] != 0.0f && idx[o] + 1 >= n_in) return fail(P3D_ERR_INVALID, "%s: output line %d interpolates past the last source line", axis, o);
     }
     return P3D_OK;
 }
@@ -85,41 +65,39 @@ extern "C" {
 int p3d_upsample(int device, const void* x, int dtype, size_t nslices, int ny, int nx, const int* iy, const float* wy, int my, const int* ix,
                  const float* wx, int mx, void* out)
 {
-    if (!x || !out) return ufail(P3D_ERR_INVALID, "NULL buffer");
-    if (dtype != P3D_F32 && dtype != P3D_C64) return ufail(P3D_ERR_INVALID, "dtype %d: float32 (P3D_F32) or complex64 (P3D_C64)", dtype);
-    if (nslices < 1 || ny < 1 || nx < 1) return ufail(P3D_ERR_INVALID, "bad shape");
+    if (!x || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (dtype != P3D_F32 && dtype != P3D_C64) return fail(P3D_ERR_INVALID, "dtype %d: float32 (P3D_F32) or complex64 (P3D_C64)", dtype);
+    if (nslices < 1 || ny < 1 || nx < 1) return fail(P3D_ERR_INVALID, "bad shape");
     int rc = check_table(iy, wy, my, ny, "iline");
     if (rc) return rc;
     rc = check_table(ix, wx, mx, nx, "xline");
     if (rc) return rc;
-    int ndev = 0;
-    U_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return ufail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    U_TRY(hipSetDevice(device));
+    rc = use_device(device);
+    if (rc) return rc;
 
     const int C = dtype == P3D_C64 ? 2 : 1;
     const size_t in_b = (size_t)ny * nx * C * sizeof(float), out_b = (size_t)my * mx * C * sizeof(float);
     size_t free_b = 0, total_b = 0;
-    U_TRY(hipMemGetInfo(&free_b, &total_b));
+    P3D_TRY(hipMemGetInfo(&free_b, &total_b));
     size_t chunk = (free_b / 2) / (in_b + out_b);
     if (chunk > nslices) chunk = nslices;
-    if (chunk < 1) return ufail(P3D_ERR_UNSUPPORTED, "one %d x %d slice and its upsampled form do not fit in device memory", ny, nx);
+    if (chunk < 1) return fail(P3D_ERR_UNSUPPORTED, "one %d x %d slice and its upsampled form do not fit in device memory", ny, nx);
 
     DevBuf din, dout, dt;
-    U_TRY(hipMalloc(&din.p, in_b * chunk));
-    U_TRY(hipMalloc(&dout.p, out_b * chunk));
-    U_TRY(hipMalloc(&dt.p, (sizeof(int) + sizeof(float)) * (size_t)(my + mx)));
+    P3D_TRY(hipMalloc(&din.p, in_b * chunk));
+    P3D_TRY(hipMalloc(&dout.p, out_b * chunk));
+    P3D_TRY(hipMalloc(&dt.p, (sizeof(int) + sizeof(float)) * (size_t)(my + mx)));
     int* d_iy = (int*)dt.p;
     int* d_ix = d_iy + my;
     float* d_wy = (float*)(d_ix + mx);
     float* d_wx = d_wy + my;
-    U_TRY(hipMemcpy(d_iy, iy, sizeof(int) * my, hipMemcpyHostToDevice));
-    U_TRY(hipMemcpy(d_ix, ix, sizeof(int) * mx, hipMemcpyHostToDevice));
-    U_TRY(hipMemcpy(d_wy, wy, sizeof(float) * my, hipMemcpyHostToDevice));
-    U_TRY(hipMemcpy(d_wx, wx, sizeof(float) * mx, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(d_iy, iy, sizeof(int) * my, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(d_ix, ix, sizeof(int) * mx, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(d_wy, wy, sizeof(float) * my, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(d_wx, wx, sizeof(float) * mx, hipMemcpyHostToDevice));
     for (size_t s0 = 0; s0 < nslices; s0 += chunk) {
         const size_t n = nslices - s0 < chunk ? nslices - s0 : chunk;
-        U_TRY(hipMemcpy(din.p, (const char*)x + s0 * in_b, n * in_b, hipMemcpyHostToDevice));
+        P3D_TRY(hipMemcpy(din.p, (const char*)x + s0 * in_b, n * in_b, hipMemcpyHostToDevice));
         const long long total = (long long)n * my * mx;
         const long long b = (total + 255) / 256;
         const unsigned blocks = (unsigned)(b > 65535 * 16 ? 65535 * 16 : b);
@@ -127,10 +105,10 @@ int p3d_upsample(int device, const void* x, int dtype, size_t nslices, int ny, i
             upsample_kernel<2><<<blocks, 256>>>((const float*)din.p, (float*)dout.p, d_iy, d_wy, d_ix, d_wx, ny, nx, my, mx, total);
         else
             upsample_kernel<1><<<blocks, 256>>>((const float*)din.p, (float*)dout.p, d_iy, d_wy, d_ix, d_wx, ny, nx, my, mx, total);
-        U_TRY(hipGetLastError());
-        U_TRY(hipMemcpy((char*)out + s0 * out_b, dout.p, n * out_b, hipMemcpyDeviceToHost));
+        P3D_TRY(hipGetLastError());
+        P3D_TRY(hipMemcpy((char*)out + s0 * out_b, dout.p, n * out_b, hipMemcpyDeviceToHost));
     }
-    U_TRY(hipDeviceSynchronize());
+    P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;
 }
 

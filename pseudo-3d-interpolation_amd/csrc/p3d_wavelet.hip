@@ -18,17 +18,18 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "p3d.h"
 #include "p3d_fft.hpp"
+#include "p3d_host.hpp"
 #include "p3d_internal.hpp"
 #include "p3d_shrink.hpp"
 
+using p3d::fail;
+using p3d::use_device;
 using p3d::c32;
 
 namespace {
@@ -1283,22 +1284,6 @@ __global__ void wconv_kernel(const double* sums, int* done, int nslices, int ite
     if (iter > 2 && (d * d) / (cur * cur) < eps) done[s] = iter + 1;
 }
 
-int wfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define W_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return wfail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 inline unsigned blocks_for(size_t n) { const size_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
 
 }  // namespace
@@ -1391,20 +1376,17 @@ extern "C" int p3d_wavelet_plan_destroy(p3d_wplan* p)
 extern "C" int p3d_wavelet_plan_create(p3d_wplan** out, int device, int nil, int nxl, int max_slices, const double* dec_lo, const double* dec_hi,
                                        const double* rec_lo, const double* rec_hi, int flen, int level)
 {
-    if (!out || !dec_lo || !dec_hi || !rec_lo || !rec_hi) return wfail(P3D_ERR_INVALID, "NULL argument");
+    if (!out || !dec_lo || !dec_hi || !rec_lo || !rec_hi) return fail(P3D_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    if (nil < 1 || nxl < 1 || max_slices < 1 || max_slices > 65535) return wfail(P3D_ERR_INVALID, "bad shape / batch size");
-    if (flen < 2 || flen > MAXL) return wfail(P3D_ERR_UNSUPPORTED, "filter length %d: 2..%d taps are supported", flen, MAXL);
-    int ndev = 0;
-    W_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return wfail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    W_TRY(hipSetDevice(device));
+    if (nil < 1 || nxl < 1 || max_slices < 1 || max_slices > 65535) return fail(P3D_ERR_INVALID, "bad shape / batch size");
+    if (flen < 2 || flen > MAXL) return fail(P3D_ERR_UNSUPPORTED, "filter length %d: 2..%d taps are supported", flen, MAXL);
+    if (int rc = use_device(device)) return rc;
     const int nmin = nil < nxl ? nil : nxl;
     int maxlev = 0;  // pywt.dwt_max_level(min(shape), flen)
     if (nmin >= flen - 1) maxlev = (int)std::floor(std::log2((double)nmin / (flen - 1.0)));
     if (maxlev < 0) maxlev = 0;
     if (level < 0) level = maxlev;
-    if (level < 1) return wfail(P3D_ERR_UNSUPPORTED, "a %d x %d slice is too small for a %d-tap wavelet (0 levels)", nil, nxl, flen);
+    if (level < 1) return fail(P3D_ERR_UNSUPPORTED, "a %d x %d slice is too small for a %d-tap wavelet (0 levels)", nil, nxl, flen);
 
     p3d_wplan* p = new p3d_wplan;
     p->device = device; p->nil = nil; p->nxl = nxl; p->max_slices = max_slices; p->nlev = level;
@@ -1425,7 +1407,7 @@ extern "C" int p3d_wavelet_plan_create(p3d_wplan** out, int device, int nil, int
 
     auto bail = [&](const char* what, hipError_t e) {
         p3d_wavelet_plan_destroy(p);
-        return wfail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        return fail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     };
     hipError_t e;
 #define ALLOC(ptr, bytes) if ((e = hipMalloc((void**)&(ptr), (bytes))) != hipSuccess) return bail(#ptr, e)
@@ -1498,7 +1480,7 @@ extern "C" int p3d_wavelet_plan_create(p3d_wplan** out, int device, int nil, int
 
 extern "C" int p3d_wavelet_info(p3d_wplan* p, int* nlev, int64_t* ncoef, int32_t* shapes /* [(nlev+1)*2]: cA, then levels coarse -> fine */)
 {
-    if (!p) return wfail(P3D_ERR_INVALID, "NULL plan");
+    if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
     if (nlev) *nlev = p->nlev;
     if (ncoef) *ncoef = (int64_t)p->ncoef;
     if (shapes) {
@@ -1540,7 +1522,7 @@ static int w_coarse(p3d_wplan* p, int ns, const Thresh* th, bool fwd, bool inv)
     if (lt == 8) wcoarse_kernel<T, 8><<<ns, COARSE_THREADS, lds, p->stream>>>(a, p->f, t);
     else if (lt == 4) wcoarse_kernel<T, 4><<<ns, COARSE_THREADS, lds, p->stream>>>(a, p->f, t);
     else wcoarse_kernel<T, 0><<<ns, COARSE_THREADS, lds, p->stream>>>(a, p->f, t);
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -1571,7 +1553,7 @@ static int w_forward_fused(p3d_wplan* p, int ns, const Thresh* th, bool fuse_inv
         else { if (lt == 8) P3D_W_DWT(16, 8); else if (lt == 4) P3D_W_DWT(16, 4); else P3D_W_DWT(16, 0); }
 #undef P3D_W_DWT
     }
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     if (lc && lc <= l_to) return w_coarse<T>(p, ns, th, true, fuse_inverse);
     return P3D_OK;
 }
@@ -1610,7 +1592,7 @@ static int w_inverse_fused(p3d_wplan* p, int ns, const Update* u, bool coarse_do
         else { if (lt == 8) P3D_W_IDWT(16, 8); else if (lt == 4) P3D_W_IDWT(16, 4); else P3D_W_IDWT(16, 0); }
 #undef P3D_W_IDWT
     }
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -1644,7 +1626,7 @@ static int w_forward(p3d_wplan* p, int ns, const Thresh* th)
         dwt_axis_kernel<T><<<dim3(blocks_for((size_t)Wo * Ho), ns), blk, 0, p->stream>>>(hi, det + cnt, det + 2 * cnt, p->f, Wo, H, Ho, 1, (size_t)Wo, (size_t)H * Wo,
                                                                                      1, (size_t)Wo, p->ncoef, p->ncoef, t2);
     }
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -1674,7 +1656,7 @@ static int w_inverse(p3d_wplan* p, int ns)
         idwt_axis_kernel<T><<<dim3(blocks_for((size_t)RH * RW), ns), blk, 0, p->stream>>>(lo, hi, as<T>(p->rec[l - 1]), p->f, RH, Wo, RW, (size_t)Wo, 1, (size_t)RH * Wo,
                                                                                       (size_t)Wo, 1, (size_t)RH * Wo, (size_t)RW, 1, (size_t)RH * RW);
     }
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -1691,10 +1673,10 @@ static bool on_plan_device(const p3d_wplan* p, const void* ptr)
 
 static int w_check(p3d_wplan* p, int nslices, int dtype)
 {
-    if (!p) return wfail(P3D_ERR_INVALID, "NULL plan");
-    if (nslices < 1 || nslices > p->max_slices) return wfail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
-    if (dtype != P3D_C64 && dtype != P3D_F32) return wfail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    W_TRY(hipSetDevice(p->device));
+    if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
+    if (nslices < 1 || nslices > p->max_slices) return fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
+    if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    P3D_TRY(hipSetDevice(p->device));
     return P3D_OK;
 }
 
@@ -1705,11 +1687,11 @@ static int w_stats(p3d_wplan* p, int dtype, int nslices)
                                                                                 p->nil, p->nxl, nullptr, 0);
     int rc = w_forward<T>(p, nslices, nullptr);
     if (rc) return rc;
-    if (p->nlev > WSTAT_MAX_LEVELS) return wfail(P3D_ERR_UNSUPPORTED, "more than %d levels", WSTAT_MAX_LEVELS);
+    if (p->nlev > WSTAT_MAX_LEVELS) return fail(P3D_ERR_UNSUPPORTED, "more than %d levels", WSTAT_MAX_LEVELS);
     WStatLevels lv{};
     for (int l = p->nlev, i = 0; l >= 1; --l, ++i) { lv.off[i] = p->doff[l]; lv.count[i] = (size_t)p->h[l] * p->w[l]; }
     wstats_kernel<T><<<dim3(p->nlev, nslices, 3), 256, 0, p->stream>>>(as<T>(p->coef), p->ncoef, lv, p->stats, p->nlev);
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -1793,7 +1775,7 @@ static int w_loop(p3d_wplan* p, int dtype, int nslices, const p3d_pocs_params* p
             if (rc) return rc;
         }
     }
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -1804,11 +1786,11 @@ int p3d_wavedec2_c64(p3d_wplan* p, const void* x, void* coef, int nslices)
 {
     int rc = w_check(p, nslices, P3D_C64);
     if (rc) return rc;
-    if (!x || !coef) return wfail(P3D_ERR_INVALID, "NULL buffer");
-    W_TRY(hipMemcpy(p->feed, x, sizeof(c32) * p->per() * nslices, hipMemcpyHostToDevice));
+    if (!x || !coef) return fail(P3D_ERR_INVALID, "NULL buffer");
+    P3D_TRY(hipMemcpy(p->feed, x, sizeof(c32) * p->per() * nslices, hipMemcpyHostToDevice));
     if ((rc = w_forward<c32>(p, nslices, nullptr))) return rc;
-    W_TRY(hipStreamSynchronize(p->stream));
-    W_TRY(hipMemcpy(coef, p->coef, sizeof(c32) * p->ncoef * nslices, hipMemcpyDeviceToHost));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpy(coef, p->coef, sizeof(c32) * p->ncoef * nslices, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
@@ -1816,15 +1798,15 @@ int p3d_waverec2_c64(p3d_wplan* p, const void* coef, void* x, int nslices)
 {
     int rc = w_check(p, nslices, P3D_C64);
     if (rc) return rc;
-    if (!x || !coef) return wfail(P3D_ERR_INVALID, "NULL buffer");
-    W_TRY(hipMemcpy(p->coef, coef, sizeof(c32) * p->ncoef * nslices, hipMemcpyHostToDevice));
+    if (!x || !coef) return fail(P3D_ERR_INVALID, "NULL buffer");
+    P3D_TRY(hipMemcpy(p->coef, coef, sizeof(c32) * p->ncoef * nslices, hipMemcpyHostToDevice));
     if ((rc = w_inverse<c32>(p, nslices))) return rc;
     // crop to the slice shape (POCS.py:513, 609)
     for (int s = 0; s < nslices; ++s)
-        W_TRY(hipMemcpy2DAsync(p->feed + (size_t)s * p->per(), sizeof(c32) * p->nxl, p->rec[0] + (size_t)s * p->rh[0] * p->rw[0], sizeof(c32) * p->rw[0],
+        P3D_TRY(hipMemcpy2DAsync(p->feed + (size_t)s * p->per(), sizeof(c32) * p->nxl, p->rec[0] + (size_t)s * p->rh[0] * p->rw[0], sizeof(c32) * p->rw[0],
                                sizeof(c32) * p->nxl, (size_t)p->nil, hipMemcpyDeviceToDevice, p->stream));
-    W_TRY(hipStreamSynchronize(p->stream));
-    W_TRY(hipMemcpy(x, p->feed, sizeof(c32) * p->per() * nslices, hipMemcpyDeviceToHost));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpy(x, p->feed, sizeof(c32) * p->per() * nslices, hipMemcpyDeviceToHost));
     return P3D_OK;
 }
 
@@ -1834,25 +1816,25 @@ int p3d_wavelet_stats(p3d_wplan* p, const void* x, int dtype, int nslices, doubl
 {
     int rc = w_check(p, nslices, dtype);
     if (rc) return rc;
-    if (!x || !stats) return wfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
     const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
     if (on_plan_device(p, x)) {
         p->cur_x = x;
     } else {
-        W_TRY(hipMemcpyAsync(p->st_x, x, esz * p->per() * nslices, hipMemcpyDefault, p->stream));   // (ordered with the plan's stream: p3d_wavelet_run)
+        P3D_TRY(hipMemcpyAsync(p->st_x, x, esz * p->per() * nslices, hipMemcpyDefault, p->stream));   // (ordered with the plan's stream: p3d_wavelet_run)
         p->cur_x = p->st_x;
     }
     if (p->sums_cap < (size_t)nslices) {
         if (p->sums) hipFree(p->sums);
         p->sums = nullptr; p->sums_cap = 0;
-        W_TRY(hipMalloc((void**)&p->sums, sizeof(double) * 2 * p->max_slices));
+        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * 2 * p->max_slices));
         p->sums_cap = 2 * (size_t)p->max_slices;
     }
-    W_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nslices, p->stream));
+    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nslices, p->stream));
     if ((rc = dtype == P3D_F32 ? w_stats<float>(p, dtype, nslices) : w_stats<c32>(p, dtype, nslices))) return rc;
     std::vector<float> host((size_t)nslices * p->nlev * 12);
-    W_TRY(hipMemcpyAsync(host.data(), p->stats, sizeof(float) * host.size(), hipMemcpyDeviceToHost, p->stream));
-    W_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpyAsync(host.data(), p->stats, sizeof(float) * host.size(), hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     for (size_t i = 0; i < host.size(); ++i) stats[i] = host[i];
     return P3D_OK;
 }
@@ -1863,23 +1845,23 @@ int p3d_wavelet_run(p3d_wplan* p, const void* x, int dtype, const float* mask, c
 {
     int rc = w_check(p, nslices, dtype);
     if (rc) return rc;
-    if (!x || !mask || !tau || !prm || !out) return wfail(P3D_ERR_INVALID, "NULL argument");
-    if (prm->niter < 1) return wfail(P3D_ERR_INVALID, "niter must be >= 1");
+    if (!x || !mask || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
     if (prm->thresh_op < P3D_OP_HARD || prm->thresh_op > P3D_OP_GARROTE)
-        return wfail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the wavelet transform", prm->thresh_op);
+        return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the wavelet transform", prm->thresh_op);
     const int niter = prm->niter;
     const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
     const size_t ntau = (size_t)nslices * niter * p->nlev * 3, nsum = (size_t)(niter + 1) * nslices;
     if (p->tau_cap < ntau) {
         if (p->tau) hipFree(p->tau);
         p->tau = nullptr; p->tau_cap = 0;
-        W_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * ntau));
+        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * ntau));
         p->tau_cap = ntau;
     }
     if (p->sums_cap < nsum) {
         if (p->sums) hipFree(p->sums);
         p->sums = nullptr; p->sums_cap = 0;
-        W_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
+        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
         p->sums_cap = nsum;
     }
     std::vector<c32> tau_f(ntau);
@@ -1896,7 +1878,7 @@ int p3d_wavelet_run(p3d_wplan* p, const void* x, int dtype, const float* mask, c
     if (on_plan_device(p, x)) {
         p->cur_x = x;
     } else {
-        W_TRY(hipMemcpyAsync(p->st_x, x, cube_bytes, hipMemcpyDefault, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->st_x, x, cube_bytes, hipMemcpyDefault, p->stream));
         p->cur_x = p->st_x;
     }
     // (the loop reads the observed cube in every iteration: a result buffer that overlaps it goes through the staging buffer)
@@ -1906,33 +1888,33 @@ int p3d_wavelet_run(p3d_wplan* p, const void* x, int dtype, const float* mask, c
     p->cur_out = direct_out ? out : p->st_out;
     // the mask may be a device pointer: a device-to-device hipMemcpy runs on the null stream, need not have finished when it returns, and the plan's
     // (non-blocking) stream does not wait for it -- every copy of this entry point goes onto the plan's stream
-    W_TRY(hipMemcpyAsync(p->mask, mask, sizeof(float) * p->per(), hipMemcpyDefault, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(float) * p->per(), hipMemcpyDefault, p->stream));
     p->mask_binary = 0;
     if ((p->l1fuse_c || p->l1fuse_r) && !getenv("P3D_WAVELET_NO_MASK_BITS")) {   // wfuse1_kernel reads a 0 / 1 mask as bits
         int* flag = reinterpret_cast<int*>(p->mask_bits + (size_t)p->nil * p->mask_words);
         const int one = 1, nw = p->nil * p->mask_words;
-        W_TRY(hipMemcpyAsync(flag, &one, sizeof(int), hipMemcpyHostToDevice, p->stream));
+        P3D_TRY(hipMemcpyAsync(flag, &one, sizeof(int), hipMemcpyHostToDevice, p->stream));
         wmask_pack_kernel<<<(nw + 255) / 256, 256, 0, p->stream>>>(p->mask, p->mask_bits, p->nil, p->nxl, p->mask_words, flag);
-        W_TRY(hipMemcpyAsync(&p->mask_binary, flag, sizeof(int), hipMemcpyDeviceToHost, p->stream));
-        W_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(hipMemcpyAsync(&p->mask_binary, flag, sizeof(int), hipMemcpyDeviceToHost, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
     }
-    W_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
-    W_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    W_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    W_TRY(hipEventRecord(p->ev0, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
+    P3D_TRY(hipEventRecord(p->ev0, p->stream));
     if ((rc = real_path ? w_loop<float>(p, dtype, nslices, prm) : w_loop<c32>(p, dtype, nslices, prm))) return rc;
-    W_TRY(hipEventRecord(p->ev1, p->stream));
-    W_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) W_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-    W_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipEventRecord(p->ev1, p->stream));
+    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
+    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     if (!direct_out) {
-        W_TRY(hipMemcpyAsync(out, p->st_out, cube_bytes, hipMemcpyDefault, p->stream));
-        W_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(hipMemcpyAsync(out, p->st_out, cube_bytes, hipMemcpyDefault, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
     }
     if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
     if (elapsed_ms) {
         float ms = 0.f;
-        W_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
         *elapsed_ms = ms;
     }
     return P3D_OK;

@@ -14,15 +14,17 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "p3d.h"
 #include "p3d_fft.hpp"
+#include "p3d_host.hpp"
 #include "p3d_internal.hpp"
+
+using p3d::fail;
+using p3d::use_device;
 
 namespace {
 
@@ -320,22 +322,6 @@ __global__ void wconv64_kernel(const double* sums, int* done, int nslices, int i
     if (iter > 2 && (d * d) / (cur * cur) < eps) done[s] = iter + 1;   // POCS.py:622, 631
 }
 
-int wfail(int code, const char* fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    p3d::set_last_error(buf);
-    return code;
-}
-#define W_TRY(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return wfail(P3D_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 inline unsigned blocks_for(size_t n) { const size_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
 
 }  // namespace
@@ -379,21 +365,18 @@ extern "C" int p3d_wavelet64_plan_destroy(p3d_wplan64* p)
 extern "C" int p3d_wavelet64_plan_create(p3d_wplan64** out, int device, int nil, int nxl, int max_slices, const double* dec_lo, const double* dec_hi,
                                          const double* rec_lo, const double* rec_hi, int flen, int level)
 {
-    if (!out || !dec_lo || !dec_hi || !rec_lo || !rec_hi) return wfail(P3D_ERR_INVALID, "NULL argument");
+    if (!out || !dec_lo || !dec_hi || !rec_lo || !rec_hi) return fail(P3D_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    if (nil < 1 || nxl < 1 || max_slices < 1 || max_slices > 65535) return wfail(P3D_ERR_INVALID, "bad shape / batch size");
-    if (flen < 2 || flen > MAXL) return wfail(P3D_ERR_UNSUPPORTED, "filter length %d: 2..%d taps are supported", flen, MAXL);
-    int ndev = 0;
-    W_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return wfail(P3D_ERR_INVALID, "device %d out of range (%d visible)", device, ndev);
-    W_TRY(hipSetDevice(device));
+    if (nil < 1 || nxl < 1 || max_slices < 1 || max_slices > 65535) return fail(P3D_ERR_INVALID, "bad shape / batch size");
+    if (flen < 2 || flen > MAXL) return fail(P3D_ERR_UNSUPPORTED, "filter length %d: 2..%d taps are supported", flen, MAXL);
+    if (int rc = use_device(device)) return rc;
     const int nmin = nil < nxl ? nil : nxl;
     int maxlev = 0;   // pywt.dwt_max_level(min(shape), flen)
     if (nmin >= flen - 1) maxlev = (int)std::floor(std::log2((double)nmin / (flen - 1.0)));
     if (maxlev < 0) maxlev = 0;
     if (level < 0) level = maxlev;
-    if (level < 1) return wfail(P3D_ERR_UNSUPPORTED, "a %d x %d slice is too small for a %d-tap wavelet (0 levels)", nil, nxl, flen);
-    if (level > WSTAT_MAX_LEVELS) return wfail(P3D_ERR_UNSUPPORTED, "more than %d levels", WSTAT_MAX_LEVELS);
+    if (level < 1) return fail(P3D_ERR_UNSUPPORTED, "a %d x %d slice is too small for a %d-tap wavelet (0 levels)", nil, nxl, flen);
+    if (level > WSTAT_MAX_LEVELS) return fail(P3D_ERR_UNSUPPORTED, "more than %d levels", WSTAT_MAX_LEVELS);
 
     p3d_wplan64* p = new p3d_wplan64;
     p->device = device; p->nil = nil; p->nxl = nxl; p->max_slices = max_slices; p->nlev = level; p->flen = flen;
@@ -409,7 +392,7 @@ extern "C" int p3d_wavelet64_plan_create(p3d_wplan64** out, int device, int nil,
 
     auto bail = [&](const char* what, hipError_t e) {
         p3d_wavelet64_plan_destroy(p);
-        return wfail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+        return fail(P3D_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
     };
     hipError_t e;
 #define ALLOC(ptr, bytes) if ((e = hipMalloc((void**)&(ptr), (bytes))) != hipSuccess) return bail(#ptr, e)
@@ -444,7 +427,7 @@ extern "C" int p3d_wavelet64_plan_create(p3d_wplan64** out, int device, int nil,
 
 extern "C" int p3d_wavelet64_info(p3d_wplan64* p, int* nlev, int64_t* ncoef)
 {
-    if (!p) return wfail(P3D_ERR_INVALID, "NULL plan");
+    if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
     if (nlev) *nlev = p->nlev;
     if (ncoef) *ncoef = (int64_t)p->ncoef;
     return P3D_OK;
@@ -483,7 +466,7 @@ static int w_forward(p3d_wplan64* p, int ns, const Thresh64* th, const int* done
         dwt_axis64_kernel<T><<<dim3(blocks_for((size_t)Wo * Ho), ns), blk, 0, p->stream>>>(hi, det + cnt, det + 2 * cnt, p->f, Wo, H, Ho, 1, (size_t)Wo, (size_t)H * Wo,
                                                                                        1, (size_t)Wo, p->ncoef, p->ncoef, t2);
     }
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -510,7 +493,7 @@ static int w_inverse(p3d_wplan64* p, int ns, const int* done)
         idwt_axis64_kernel<T><<<dim3(blocks_for((size_t)RH * RW), ns), blk, 0, p->stream>>>(lo, hi, as<T>(p->rec[l - 1]), p->f, RH, Wo, RW, (size_t)Wo, 1, (size_t)RH * Wo,
                                                                                         (size_t)Wo, 1, (size_t)RH * Wo, (size_t)RW, 1, (size_t)RH * RW, done);
     }
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -529,10 +512,10 @@ static bool real_dtype(int dtype) { return dtype == P3D_F64 || dtype == P3D_F32;
 
 static int w_check(p3d_wplan64* p, int nslices, int dtype)
 {
-    if (!p) return wfail(P3D_ERR_INVALID, "NULL plan");
-    if (nslices < 1 || nslices > p->max_slices) return wfail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
-    if (dtype != P3D_C64 && dtype != P3D_F32 && dtype != P3D_C128 && dtype != P3D_F64) return wfail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    W_TRY(hipSetDevice(p->device));
+    if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
+    if (nslices < 1 || nslices > p->max_slices) return fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
+    if (dtype != P3D_C64 && dtype != P3D_F32 && dtype != P3D_C128 && dtype != P3D_F64) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    P3D_TRY(hipSetDevice(p->device));
     return P3D_OK;
 }
 
@@ -541,7 +524,7 @@ static int ensure_sums(p3d_wplan64* p, size_t n)
     if (p->sums_cap < n) {
         if (p->sums) hipFree(p->sums);
         p->sums = nullptr; p->sums_cap = 0;
-        W_TRY(hipMalloc((void**)&p->sums, sizeof(double) * n));
+        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * n));
         p->sums_cap = n;
     }
     return P3D_OK;
@@ -557,7 +540,7 @@ static int w_stats(p3d_wplan64* p, int dtype, int nslices)
     WStatLevels lv{};
     for (int l = p->nlev, i = 0; l >= 1; --l, ++i) { lv.off[i] = p->doff[l]; lv.count[i] = (size_t)p->h[l] * p->w[l]; }
     wstats64_kernel<T><<<dim3(p->nlev, nslices, 3), 256, 0, p->stream>>>(as<T>(p->coef), p->ncoef, lv, p->stats, p->nlev);
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -583,7 +566,7 @@ static int w_loop(p3d_wplan64* p, int dtype, int nslices, const p3d_pocs_params*
         wrowsum64_kernel<<<nslices, 256, 0, p->stream>>>(p->rowsum, p->sums + (size_t)(k + 1) * nslices, p->nil, p->done);
         if (early) wconv64_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
     }
-    W_TRY(hipGetLastError());
+    P3D_TRY(hipGetLastError());
     return P3D_OK;
 }
 
@@ -595,16 +578,16 @@ int p3d_wavelet64_stats(p3d_wplan64* p, const void* x, int dtype, int nslices, d
 {
     int rc = w_check(p, nslices, dtype);
     if (rc) return rc;
-    if (!x || !stats) return wfail(P3D_ERR_INVALID, "NULL buffer");
+    if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
     if (on_plan_device(p, x)) {
         p->cur_x = x;
     } else {
-        W_TRY(hipMemcpyAsync(p->st_x, x, elem_bytes(dtype) * p->per() * nslices, hipMemcpyDefault, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->st_x, x, elem_bytes(dtype) * p->per() * nslices, hipMemcpyDefault, p->stream));
         p->cur_x = p->st_x;
     }
     if ((rc = real_dtype(dtype) ? w_stats<double>(p, dtype, nslices) : w_stats<c64>(p, dtype, nslices))) return rc;
-    W_TRY(hipMemcpyAsync(stats, p->stats, sizeof(double) * (size_t)nslices * p->nlev * 12, hipMemcpyDeviceToHost, p->stream));
-    W_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpyAsync(stats, p->stats, sizeof(double) * (size_t)nslices * p->nlev * 12, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     return P3D_OK;
 }
 
@@ -615,16 +598,16 @@ int p3d_wavelet64_run(p3d_wplan64* p, const void* x, int dtype, const double* ma
 {
     int rc = w_check(p, nslices, dtype);
     if (rc) return rc;
-    if (!x || !mask || !tau || !prm || !out) return wfail(P3D_ERR_INVALID, "NULL argument");
-    if (prm->niter < 1) return wfail(P3D_ERR_INVALID, "niter must be >= 1");
+    if (!x || !mask || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
     if (prm->thresh_op < P3D_OP_HARD || prm->thresh_op > P3D_OP_GARROTE)
-        return wfail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the wavelet transform", prm->thresh_op);
+        return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the wavelet transform", prm->thresh_op);
     const int niter = prm->niter;
     const size_t ntau = (size_t)nslices * niter * p->nlev * 3, nsum = (size_t)(niter + 1) * nslices;
     if (p->tau_cap < ntau) {
         if (p->tau) hipFree(p->tau);
         p->tau = nullptr; p->tau_cap = 0;
-        W_TRY(hipMalloc((void**)&p->tau, sizeof(c64) * ntau));
+        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c64) * ntau));
         p->tau_cap = ntau;
     }
     if ((rc = ensure_sums(p, nsum))) return rc;
@@ -638,7 +621,7 @@ int p3d_wavelet64_run(p3d_wplan64* p, const void* x, int dtype, const double* ma
     if (on_plan_device(p, x)) {
         p->cur_x = x;
     } else {
-        W_TRY(hipMemcpyAsync(p->st_x, x, cube_bytes, hipMemcpyDefault, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->st_x, x, cube_bytes, hipMemcpyDefault, p->stream));
         p->cur_x = p->st_x;
     }
     // (the loop reads the observed cube in every iteration: a result buffer that overlaps it goes through the staging buffer)
@@ -647,24 +630,24 @@ int p3d_wavelet64_run(p3d_wplan64* p, const void* x, int dtype, const double* ma
     const bool direct_out = on_plan_device(p, out) && (ob + cube_bytes <= xb || xb + cube_bytes <= ob);
     p->cur_out = direct_out ? out : p->st_out;
     // every copy goes onto the plan's (non-blocking) stream: a device-to-device hipMemcpy on the null stream need not have finished when it returns
-    W_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * p->per(), hipMemcpyDefault, p->stream));
-    W_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));
-    W_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    W_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    W_TRY(hipEventRecord(p->ev0, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * p->per(), hipMemcpyDefault, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
+    P3D_TRY(hipEventRecord(p->ev0, p->stream));
     if ((rc = real_path ? w_loop<double>(p, dtype, nslices, prm) : w_loop<c64>(p, dtype, nslices, prm))) return rc;
-    W_TRY(hipEventRecord(p->ev1, p->stream));
-    W_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) W_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-    W_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipEventRecord(p->ev1, p->stream));
+    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
+    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
     if (!direct_out) {
-        W_TRY(hipMemcpyAsync(out, p->st_out, cube_bytes, hipMemcpyDefault, p->stream));
-        W_TRY(hipStreamSynchronize(p->stream));
+        P3D_TRY(hipMemcpyAsync(out, p->st_out, cube_bytes, hipMemcpyDefault, p->stream));
+        P3D_TRY(hipStreamSynchronize(p->stream));
     }
     if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
     if (elapsed_ms) {
         float ms = 0.f;
-        W_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
         *elapsed_ms = ms;
     }
     return P3D_OK;

@@ -1,5 +1,5 @@
 """CPU-only checks of the product's host side: threshold schedule vs the reference's golden vectors,
-error contract of POCS_algorithm, C-ABI surface of libp3d_hip.so, host emulation of the FFT engine."""
+error contract of POCS_algorithm, C-ABI surface of libp3d_hip.so, host emulation of the FFT engine, the shared host helpers."""
 import ctypes
 import os
 import re
@@ -199,6 +199,17 @@ def test_fft_engine_host_emulation(tmp_path):
                     "-o", str(exe)], check=True)
     res = subprocess.run([str(exe)], capture_output=True, text=True)
     assert res.returncode == 0, res.stdout[-2000:]
+    assert "ALL OK" in res.stdout
+
+
+def test_shared_host_helpers(tmp_path):
+    """csrc/p3d_host.hpp on the CPU (tests/csrc/test_host_helpers.cpp): p3d::fail returns its code, formats its arguments and cuts a 2000-character
+    message to 511 characters; P3D_TRY leaves with P3D_ERR_HIP and '<expression> failed: <runtime's text>'; an empty DevBuf never calls hipFree."""
+    exe = tmp_path / "host_helpers"
+    subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-I", CSRC,
+                    "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "csrc", "test_host_helpers.cpp"), "-o", str(exe)], check=True)
+    res = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
     assert "ALL OK" in res.stdout
 
 
