@@ -521,6 +521,26 @@ int p3d_mistie_nearest(int device, const double* xy, const long long* line_off, 
 int p3d_mistie_xcorr(int device, const float* a, const float* b, size_t ncross, int ns, const int* ranges, int path, int* shift, double* coeff, int* n,
                      int* status);
 
+/* ---- steps 3 and 4: DelayRecordingTime correction and padding (p3d_delrt.hip; the reference's delrt_correction_segy.py / delrt_padding_segy.py) ----
+ * Sections are trace-major float32 and start at 16-byte boundaries (any hipMalloc'ed buffer does).  Both operations only copy and compare, so the
+ * results are bit-identical to NumPy's; NaN samples are outside the contract (a comparison with NaN never holds: NaNs are skipped).
+ *   pad:     out[x][t] = in[x][t - top[x]] for top[x] <= t < top[x] + ns_in, else 0; in [ntr][ns_in], out [ntr][ns_out], ns_out >= ns_in, top one int
+ *            per trace; in and out must not overlap.  top[x] < 0 or top[x] + ns_in > ns_out: P3D_ERR_INVALID before anything is launched (the _dev
+ *            entry copies its DEVICE table back for this check).
+ *   windows: for delay change c with reference trace ref[c] (n_traces <= ref[c] <= ntr - 1 - n_traces, else P3D_ERR_INVALID before the launch):
+ *            peak_val[c] = the maximum of trace ref[c] and peak_idx[c] = the FIRST row that holds it (np.argmax);
+ *            maxima[c][j], j = 0 ... 2 n_traces = the maximum of trace ref[c] - n_traces + j over rows [max(peak_idx - n_samples / 2, 0),
+ *            min(peak_idx + n_samples / 2 + 1, ns)) -- the plain maximum: the reference's clipping to peak_val is left to the caller.
+ *            All changes of a file go in one launch (m = 0: nothing is done).  n_traces >= 1, n_samples >= 1.
+ * p3d_delrt_pad_dev: all pointers DEVICE.  p3d_delrt_windows_dev: the section and the three results DEVICE, ref HOST (m entries, a small table).
+ * p3d_delrt_pad / p3d_delrt_windows take HOST arrays; windows takes the packed subsets [m][2 n_traces + 1][ns] (only the traces that are needed
+ * cross the bus), which are a section of their own with ref[c] = c (2 n_traces + 1) + n_traces: the same kernel serves both forms. */
+int p3d_delrt_pad_dev(int device, const float* in_dev, int ntr, int ns_in, int ns_out, const int* top_dev, float* out_dev);
+int p3d_delrt_pad(int device, const float* section, int ntr, int ns_in, int ns_out, const int* top, float* out);
+int p3d_delrt_windows_dev(int device, const float* section_dev, int ntr, int ns, const int* ref, int m, int n_traces, int n_samples, int* peak_idx_dev,
+                          float* peak_val_dev, float* maxima_dev);
+int p3d_delrt_windows(int device, const float* subsets, int m, int ns, int n_traces, int n_samples, int* peak_idx, float* peak_val, float* maxima);
+
 #ifdef __cplusplus
 }
 #endif

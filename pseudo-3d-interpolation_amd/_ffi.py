@@ -139,6 +139,10 @@ PROTOTYPES = {
     "p3d_mistie_nearest": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "p3d_mistie_xcorr": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "p3d_delrt_pad_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_delrt_pad": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_delrt_windows_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3d_delrt_windows": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1435,6 +1439,56 @@ def static_shift(section, shift, device=0):
     out = np.empty_like(section)
     check(lib().p3d_static_shift(int(device), _ptr(section), section.shape[0], section.shape[1], _ptr(shift), _ptr(out)))
     return out
+
+
+# ---- steps 3 and 4: DelayRecordingTime correction and padding (include/p3d.h, p3d_delrt.hip) ------------------------
+def _delrt_window(n_traces, n_samples):
+    n_traces, n_samples = int(n_traces), int(n_samples)
+    if n_traces < 1 or n_samples < 1:
+        raise ValueError(f"the comparison window needs at least 1 trace to either side and 1 sample, got n_traces={n_traces}, n_samples={n_samples}")
+    return n_traces, n_samples
+
+
+def delrt_pad_dev(section, ntr, ns_in, ns_out, top, out, device=0):
+    """p3d_delrt_pad_dev on device pointers: out[x][t] = section[x][t - top[x]] or 0, ``out`` [ntr][ns_out] another buffer than ``section``
+    [ntr][ns_in], ``top`` int32 [ntr] with 0 <= top[x] <= ns_out - ns_in (else the library refuses before it launches anything)."""
+    check(lib().p3d_delrt_pad_dev(int(device), section, int(ntr), int(ns_in), int(ns_out), top, out))
+
+
+def delrt_pad(section, top, ns_out, device=0):
+    """Zero-pad the traces of a host section [ntr][ns_in] to ``ns_out`` samples, trace x behind ``top[x]`` zeros (p3d_delrt_pad)."""
+    section = _static_section(section)
+    top = np.ascontiguousarray(top, dtype=np.int32)
+    if top.shape != (section.shape[0],):
+        raise ValueError("one top padding per trace")
+    ns_out = int(ns_out)
+    if ns_out < 1:
+        raise ValueError(f"padded traces of {ns_out} samples")
+    out = np.empty((section.shape[0], ns_out), np.float32)
+    check(lib().p3d_delrt_pad(int(device), _ptr(section), section.shape[0], section.shape[1], ns_out, _ptr(top), _ptr(out)))
+    return out
+
+
+def delrt_windows_dev(section, ntr, ns, ref, n_traces, n_samples, peak_idx, peak_val, maxima, device=0):
+    """p3d_delrt_windows_dev: ``section`` and the three results are device pointers (int32 [m], float32 [m], float32 [m][2 n_traces + 1]),
+    ``ref`` a HOST array of the m reference-trace indices."""
+    n_traces, n_samples = _delrt_window(n_traces, n_samples)
+    ref = np.ascontiguousarray(ref, dtype=np.int32).ravel()
+    check(lib().p3d_delrt_windows_dev(int(device), section, int(ntr), int(ns), _ptr(ref), ref.size, n_traces, n_samples, peak_idx, peak_val, maxima))
+
+
+def delrt_windows(subsets, n_samples, device=0):
+    """Peak and window maxima of the packed subsets [m][2 n_traces + 1][ns] of m delay changes (p3d_delrt_windows).  Returns ``(peak_idx,
+    peak_val, maxima)``: int32 [m] first row of the maximum of every reference trace (the middle one), float32 [m] that maximum, float32
+    [m][2 n_traces + 1] the maxima of all traces within n_samples // 2 rows of it."""
+    subsets = np.ascontiguousarray(subsets, dtype=np.float32)
+    if subsets.ndim != 3 or subsets.shape[1] % 2 != 1 or subsets.shape[1] < 3 or subsets.shape[2] < 1:
+        raise ValueError("subsets are [nchanges][2 n_traces + 1][nsamples]")
+    m, width, ns = subsets.shape
+    n_traces, n_samples = _delrt_window(width // 2, n_samples)
+    peak_idx, peak_val, maxima = np.empty(m, np.int32), np.empty(m, np.float32), np.empty((m, width), np.float32)
+    check(lib().p3d_delrt_windows(int(device), _ptr(subsets), m, ns, n_traces, n_samples, _ptr(peak_idx), _ptr(peak_val), _ptr(maxima)))
+    return peak_idx, peak_val, maxima
 
 
 # ---- step 7: mistie correction (include/p3d.h, p3d_mistie.hip) ---------------------------------------------------

@@ -7,7 +7,10 @@ and samples are read without copying the file; samples are converted to float32 
 
 Trace header fields (1-based byte positions, the ones step 10 scrapes): 1 TRACE_SEQUENCE_LINE, 5 TRACE_SEQUENCE_FILE, 9 FieldRecord,
 71 SourceGroupScalar, 73 SourceX, 77 SourceY, 109 DelayRecordingTime, 115 TRACE_SAMPLE_COUNT, 117 TRACE_SAMPLE_INTERVAL (microseconds); the ones
-step 5 reads and writes: 61 SourceWaterDepth, 69 ElevationScalar, 103 TotalStaticApplied, 233 UnassignedInt1, 237 UnassignedInt2."""
+step 5 reads and writes: 61 SourceWaterDepth, 69 ElevationScalar, 103 TotalStaticApplied, 233 UnassignedInt1, 237 UnassignedInt2.  Step 4 writes a copy
+of a file with another trace length (`write_resized`)."""
+import os
+
 import numpy as np
 
 TEXT_BYTES, BIN_BYTES, TRACE_HEADER_BYTES = 3200, 400, 240
@@ -186,6 +189,16 @@ def write_segy(path, data, dt_ms, fmt=5, headers=None, text='', binary=None):
     return path
 
 
+def _encode_samples(data, fmt):
+    """float32 samples as the values of sample format ``fmt``: IBM words (1), IEEE floats (5), or integers rounded and clipped to the format's range."""
+    if fmt == 1:
+        return ieee2ibm(data)
+    if fmt == 5:
+        return data
+    info = np.iinfo(np.dtype(SAMPLE_DTYPE[fmt]))
+    return np.clip(np.rint(data), info.min, info.max)
+
+
 def update_samples(path, data):
     """Overwrite the samples of an existing SEG-Y file in place with ``data`` [ntraces][ns] (float), encoded in the file's own sample
     format; the file, binary and trace headers are not touched.  IBM (1) and IEEE (5) floats and the integer formats are supported."""
@@ -197,13 +210,7 @@ def update_samples(path, data):
     fmt, dtype = src.format, src._dtype
     del src
     mm = np.memmap(path, dtype, 'r+', offset=start, shape=(data.shape[0],))
-    if fmt == 1:
-        mm['data'] = ieee2ibm(data)
-    elif fmt == 5:
-        mm['data'] = data
-    else:
-        info = np.iinfo(np.dtype(SAMPLE_DTYPE[fmt]))
-        mm['data'] = np.clip(np.rint(data), info.min, info.max)
+    mm['data'] = _encode_samples(data, fmt)
     mm.flush()
     del mm
     return path
@@ -233,3 +240,48 @@ def update_headers(path, fields):
     mm.flush()
     del mm
     return path
+
+
+def write_resized(src_path, dst_path, data, fields=None):
+    """Write ``data`` [ntraces][ns_new] (float) as the samples of a copy of the SEG-Y file ``src_path`` whose traces get a new length (step 4:
+    zero-padded traces).  The textual header, the binary header, the extended textual headers and every 240-byte trace header are copied
+    verbatim from the source but for: binary header ``Samples`` = ns_new and ``SamplesOriginal`` = the source's sample count; trace header
+    ``TRACE_SAMPLE_COUNT`` = ns_new and the words of ``fields`` (TRACE_FIELDS names -> one value per trace or a scalar).  The samples are
+    encoded in the source's own format.  A sample count beyond the 16 bits of the header words is an error."""
+    src = SegyFile(src_path)
+    data = np.asarray(data, dtype=np.float32)
+    if data.ndim != 2 or data.shape[0] != src.ntraces:
+        raise ValueError(f'{src_path}: holds {src.ntraces} traces, got an array of shape {data.shape}')
+    ns_new = data.shape[1]
+    if not 1 <= ns_new <= 65535:
+        raise ValueError(f'{ns_new} samples per trace do not fit the 16-bit sample count of the SEG-Y headers (at most 65535)')
+    if os.path.exists(dst_path) and os.path.samefile(src_path, dst_path):
+        raise ValueError('a file cannot be resized in place: the output must be another file')
+    start = TEXT_BYTES + BIN_BYTES + TEXT_BYTES * max(src.binary['ExtendedHeaders'], 0)
+    fmt, ntr, ns_old, old_size = src.format, src.ntraces, src.ns, src._dtype.itemsize
+    del src
+    raw = np.memmap(src_path, np.uint8, 'r')
+    head = np.array(raw[:start])
+    for name, value in (('Samples', ns_new), ('SamplesOriginal', ns_old)):
+        byte, dt = BIN_FIELDS[name]
+        head[byte - 1:byte - 1 + np.dtype(dt).itemsize] = np.frombuffer(np.array(value, dt).tobytes(), np.uint8)
+    dtype = _trace_dtype(ns_new, fmt)
+    out = np.empty((ntr, dtype.itemsize), np.uint8)
+    out[:, :TRACE_HEADER_BYTES] = raw[start:].reshape(ntr, old_size)[:, :TRACE_HEADER_BYTES]
+    del raw
+    rec = out.view(dtype).reshape(ntr)
+    words = {'TRACE_SAMPLE_COUNT': ns_new}
+    for name, values in (fields or {}).items():
+        if name not in TRACE_FIELDS:
+            raise KeyError(f'{name!r} is not one of the trace-header fields {sorted(TRACE_FIELDS)}')
+        info = np.iinfo(np.dtype(TRACE_FIELDS[name][1]))
+        if np.min(values) < info.min or np.max(values) > info.max:
+            raise OverflowError(f'{name}: values outside the range of a {info.bits}-bit header word')
+        words[name] = values
+    for name, values in words.items():
+        rec[name] = values
+    rec['data'] = _encode_samples(data, fmt)
+    with open(dst_path, 'wb') as f:
+        f.write(head.tobytes())
+        out.tofile(f)
+    return dst_path
