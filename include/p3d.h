@@ -541,6 +541,22 @@ int p3d_delrt_windows_dev(int device, const float* section_dev, int ntr, int ns,
                           float* peak_val_dev, float* maxima_dev);
 int p3d_delrt_windows(int device, const float* subsets, int m, int ns, int n_traces, int n_samples, int* peak_idx, float* peak_val, float* maxima);
 
+/* ---- step 2: reprojection of header coordinates (p3d_proj.hip; the reference's reproject_segy.py, which takes the projection from pyproj) ----
+ * Transverse Mercator between geographic degrees and projected metres on one ellipsoid, all arithmetic in double: the Krueger series in the
+ * third flattening to n^6 (Karney 2011), accurate to nanometres within a few degrees of the central meridian and to well under a micrometre
+ * over a UTM zone with its neighbours.  prm = {a, f, lon0_deg, lat0_deg, k0, x0, y0} (HOST, 7 doubles): semi-major axis, flattening,
+ * central meridian, latitude of origin, scale on the central meridian, false easting, false northing.  The series constants are computed
+ * on the host per call and passed to the kernel by value.
+ *   inverse == 0: (x, y) = (longitude, latitude) in degrees -> (ox, oy) = (easting, northing);
+ *   inverse != 0: (x, y) = (easting, northing) -> (ox, oy) = (longitude, latitude) in degrees (Newton's iteration for the latitude: 5 steps, fixed).
+ * One thread per point; ox may be x and oy may be y (in place), no other overlap.  Non-finite inputs give non-finite outputs (no error).
+ * p3d_proj_tmerc_dev: the four arrays DEVICE.  p3d_proj_tmerc: the four arrays HOST.  n = 0: nothing is done.
+ *   smooth: out[i] = sum_k padded[i + k] * w[wlen - 1 - k], k = 0 ... wlen - 1 in this order, i = 0 ... n - 1 (np.convolve(padded, w, 'valid')):
+ *   padded DEVICE with n + wlen - 1 samples, out DEVICE with n samples (another buffer), w HOST with wlen >= 1 weights. */
+int p3d_proj_tmerc_dev(int device, const double* x_dev, const double* y_dev, size_t n, const double* prm, int inverse, double* ox_dev, double* oy_dev);
+int p3d_proj_tmerc(int device, const double* x, const double* y, size_t n, const double* prm, int inverse, double* ox, double* oy);
+int p3d_proj_smooth_dev(int device, const double* padded_dev, size_t n, const double* w, int wlen, double* out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,9 @@ PROTOTYPES = {
     "p3d_delrt_pad": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "p3d_delrt_windows_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "p3d_delrt_windows": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3d_proj_tmerc_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_proj_tmerc": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_proj_smooth_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1489,6 +1492,58 @@ def delrt_windows(subsets, n_samples, device=0):
     peak_idx, peak_val, maxima = np.empty(m, np.int32), np.empty(m, np.float32), np.empty((m, width), np.float32)
     check(lib().p3d_delrt_windows(int(device), _ptr(subsets), m, ns, n_traces, n_samples, _ptr(peak_idx), _ptr(peak_val), _ptr(maxima)))
     return peak_idx, peak_val, maxima
+
+
+# ---- step 2: reprojection of header coordinates (include/p3d.h, p3d_proj.hip) --------------------------------------
+def _tmerc_prm(prm):
+    prm = np.ascontiguousarray(prm, dtype=np.float64)
+    if prm.shape != (7,):
+        raise ValueError("projection parameters are (a, f, lon0_deg, lat0_deg, k0, x0, y0)")
+    return prm
+
+
+def proj_tmerc_dev(x, y, n, prm, inverse, out_x, out_y, device=0):
+    """p3d_proj_tmerc_dev on device pointers to ``n`` float64 values each: forward (``inverse`` False: longitude / latitude in degrees ->
+    easting / northing) or inverse transverse Mercator with ``prm`` = (a, f, lon0_deg, lat0_deg, k0, x0, y0).  ``out_x`` may be ``x`` and
+    ``out_y`` may be ``y``."""
+    prm = _tmerc_prm(prm)
+    check(lib().p3d_proj_tmerc_dev(int(device), x, y, int(n), _ptr(prm), int(bool(inverse)), out_x, out_y))
+
+
+def proj_tmerc(x, y, prm, inverse=False, device=0):
+    """Forward or inverse transverse Mercator of host arrays (p3d_proj_tmerc).  Returns two float64 arrays of the inputs' shape."""
+    x, y = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(y, dtype=np.float64)
+    if x.shape != y.shape:
+        raise ValueError(f"x {x.shape} and y {y.shape} differ in shape")
+    prm = _tmerc_prm(prm)
+    ox, oy = np.empty_like(x), np.empty_like(y)
+    check(lib().p3d_proj_tmerc(int(device), _ptr(x), _ptr(y), x.size, _ptr(prm), int(bool(inverse)), _ptr(ox), _ptr(oy)))
+    return ox, oy
+
+
+def proj_smooth_dev(padded, n, w, out, device=0):
+    """p3d_proj_smooth_dev: ``padded`` (n + len(w) - 1 float64) and ``out`` (n float64) are device pointers, ``w`` a HOST array of weights;
+    out = np.convolve(padded, w, 'valid')."""
+    w = np.ascontiguousarray(w, dtype=np.float64).ravel()
+    if w.size < 1:
+        raise ValueError("an empty window")
+    check(lib().p3d_proj_smooth_dev(int(device), padded, int(n), _ptr(w), w.size, out))
+
+
+def proj_smooth(padded, w, device=0):
+    """np.convolve(padded, w, 'valid') of a host signal on the device (len(padded) >= len(w) >= 1), in double."""
+    padded, w = np.ascontiguousarray(padded, dtype=np.float64).ravel(), np.ascontiguousarray(w, dtype=np.float64).ravel()
+    n = padded.size - w.size + 1
+    if w.size < 1 or n < 1:
+        raise ValueError(f"a signal of {padded.size} samples and a window of {w.size}")
+    din, dout = DeviceArray((padded.size,), np.float64, device), DeviceArray((n,), np.float64, device)
+    try:
+        din.upload(padded)
+        proj_smooth_dev(din.ptr, n, w, dout.ptr, device)
+        return dout.download()
+    finally:
+        din.free()
+        dout.free()
 
 
 # ---- step 7: mistie correction (include/p3d.h, p3d_mistie.hip) ---------------------------------------------------

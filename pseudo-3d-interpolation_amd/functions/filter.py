@@ -436,3 +436,42 @@ def moving_window_2D(a, w, dx=1, dy=1, writeable=False):
     nrow, ncol = (a.shape[-2] - w[-2]) // dy + 1, (a.shape[-1] - w[-1]) // dx + 1
     return np.lib.stride_tricks.as_strided(a, shape=a.shape[:-2] + (nrow, ncol) + w,
                                            strides=a.strides[:-2] + (a.strides[-2] * dy, a.strides[-1] * dx) + a.strides[-2:], writeable=writeable)
+
+
+# ---- step 2: smoothing of a coordinate profile ----------------------------------------------------------------------------------
+SMOOTH_WINDOWS = {'flat': np.ones, 'hanning': np.hanning, 'hamming': np.hamming, 'bartlett': np.bartlett, 'blackman': np.blackman}
+
+
+def _line_fit(values):
+    """Slope and intercept of the least-squares line through ``values`` at 0, 1, ... (the minimum-norm solution for a single value)."""
+    design = np.column_stack([np.arange(values.size), np.ones(values.size)])
+    return np.linalg.lstsq(design, values, rcond=None)[0]
+
+
+def smooth_padded(data, window_len, window='hanning'):
+    """Host half of :func:`smooth` for an odd ``window_len`` >= 3: the signal with ``window_len // 2`` samples added at each end on the
+    least-squares lines through its first and its last ``window_len // 2`` samples, and the window normalised to a sum of 1."""
+    half = window_len // 2
+    m0, c0 = _line_fit(data[:half])
+    m1, c1 = _line_fit(data[-half:])
+    padded = np.r_[np.arange(-half, 0, 1) * m0 + c0, data, np.arange(half, 2 * half) * m1 + c1]
+    w = np.asarray(SMOOTH_WINDOWS[window](window_len), dtype=np.float64)
+    return padded, w / w.sum()
+
+
+def smooth(data, window_len=11, window='hanning', device=0):
+    """Smooth a 1-D array with a normalised window of ``window_len`` samples (reference: functions/filter.py ``smooth``, the SciPy cookbook's
+    recipe with linearly extrapolated ends).  An even length becomes the next odd one; below 3 the input is returned as it is.  The padded signal
+    and the window are built on the host (`smooth_padded`), the convolution runs on the GPU in double (``p3d_proj_smooth_dev``).  The order of
+    the checks, and so which ``ValueError`` an input meets, is the reference's."""
+    if data.ndim != 1:
+        raise ValueError('smooth only accepts 1 dimension arrays.')
+    if data.size < window_len:
+        raise ValueError(f'Input data should be longer ({data.size}) than the window length ({window_len}).')
+    if window_len < 3:
+        return data
+    window_len += 1 - window_len % 2
+    if window not in SMOOTH_WINDOWS:
+        raise ValueError("Window is one of 'flat', 'hanning', 'hamming', 'bartlett', 'blackman'")
+    padded, w = smooth_padded(np.asarray(data, dtype=np.float64), window_len, window)
+    return _ffi.proj_smooth(padded, w, device=device)

@@ -7,8 +7,8 @@ and samples are read without copying the file; samples are converted to float32 
 
 Trace header fields (1-based byte positions, the ones step 10 scrapes): 1 TRACE_SEQUENCE_LINE, 5 TRACE_SEQUENCE_FILE, 9 FieldRecord,
 71 SourceGroupScalar, 73 SourceX, 77 SourceY, 109 DelayRecordingTime, 115 TRACE_SAMPLE_COUNT, 117 TRACE_SAMPLE_INTERVAL (microseconds); the ones
-step 5 reads and writes: 61 SourceWaterDepth, 69 ElevationScalar, 103 TotalStaticApplied, 233 UnassignedInt1, 237 UnassignedInt2.  Step 4 writes a copy
-of a file with another trace length (`write_resized`)."""
+step 5 reads and writes: 61 SourceWaterDepth, 69 ElevationScalar, 103 TotalStaticApplied, 233 UnassignedInt1, 237 UnassignedInt2; the ones step 2
+adds: 81 GroupX, 85 GroupY, 89 CoordinateUnits, 181 CDP_X, 185 CDP_Y.  Step 4 writes a copy of a file with another trace length (`write_resized`)."""
 import os
 
 import numpy as np
@@ -25,10 +25,15 @@ TRACE_FIELDS = {
     'SourceGroupScalar': (71, '>i2'),
     'SourceX': (73, '>i4'),
     'SourceY': (77, '>i4'),
+    'GroupX': (81, '>i4'),
+    'GroupY': (85, '>i4'),
+    'CoordinateUnits': (89, '>i2'),
     'TotalStaticApplied': (103, '>i2'),
     'DelayRecordingTime': (109, '>i2'),
     'TRACE_SAMPLE_COUNT': (115, '>u2'),
     'TRACE_SAMPLE_INTERVAL': (117, '>u2'),
+    'CDP_X': (181, '>i4'),
+    'CDP_Y': (185, '>i4'),
     'UnassignedInt1': (233, '>i4'),
     'UnassignedInt2': (237, '>i4'),
 }
