@@ -557,6 +557,25 @@ int p3d_proj_tmerc_dev(int device, const double* x_dev, const double* y_dev, siz
 int p3d_proj_tmerc(int device, const double* x, const double* y, size_t n, const double* prm, int inverse, double* ox, double* oy);
 int p3d_proj_smooth_dev(int device, const double* padded_dev, size_t n, const double* w, int wlen, double* out_dev);
 
+/* ---- step 6: tide compensation (p3d_tide.hip; the reference's tide_compensation_segy.py, which takes the prediction from tpxo-tide-prediction) ----
+ * Harmonic tide prediction along a track, all arithmetic in double, one thread per point.  Point i has lon[i], lat[i] in degrees and t[i] in seconds
+ * since 1992-01-01T00:00:00 (may be negative).  The tables are a SUBSET of a tidal atlas on a uniform grid: node (i, j) lies at (lon0 + i dlon,
+ * lat0 + j dlat), grid = {lon0, dlon, lat0, dlat} (HOST, 4 doubles, both spacings positive); hre / him int32 [nc][nxs][nys] hold the real and imaginary
+ * part of the elevation constants in millimetres, wet uint8 [nxs][nys] is non-zero on water; nxs, nys >= 2.  The longitudes are already unwrapped
+ * onto the subset's axis.  ids (HOST, nc ints, 1 <= nc <= P3D_TIDE_CONSTITUENTS) name the constituent of each table plane: m2, s2, n2, k2, k1, o1, p1,
+ * q1, m4, mf, 2n2, mm, mn4, ms4 = 0 ... 13, with the frequencies and phases of OTPS constit.h.
+ *   per point: the bilinear weights of the enclosing cell (a point on the last row or column uses the last cell with weights 0 / 1); the weights of
+ *   dry nodes are dropped and the rest divided by their sum; the result is NaN when the four nodes are dry or the remaining weights sum to 0, and
+ *   also for a non-finite point or one more than 1e-9 of a cell outside the subset (no table is read then).  z_c = (sum w hre + i sum w him) / 1000.
+ *   T = t / 86400 + 48622 - 51544.4993 days, N = (125.0445 - 0.05295377 T) mod 360 degrees; the nodal factor f_c and phase u_c of OTPS `nodal` from
+ *   sin / cos of N, 2 N, 3 N;  tide = sum_c f_c (Re z_c cos theta_c - Im z_c sin theta_c),  theta_c = omega_c t + phi0_c + u_c, in metres.
+ * Entry with the _dev suffix: lon, lat, t, hre, him, wet and tide DEVICE (tide a buffer of its own).  Entry without it: all of them HOST.  n = 0: nothing is done. */
+#define P3D_TIDE_CONSTITUENTS 14
+int p3d_tide_predict_dev(int device, const double* lon_dev, const double* lat_dev, const double* t_dev, size_t n, const int* hre_dev, const int* him_dev,
+                         const unsigned char* wet_dev, int nc, int nxs, int nys, const double* grid, const int* ids, double* tide_dev);
+int p3d_tide_predict(int device, const double* lon, const double* lat, const double* t, size_t n, const int* hre, const int* him, const unsigned char* wet,
+                     int nc, int nxs, int nys, const double* grid, const int* ids, double* tide);
+
 #ifdef __cplusplus
 }
 #endif

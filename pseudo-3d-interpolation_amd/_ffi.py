@@ -146,6 +146,10 @@ PROTOTYPES = {
     "p3d_proj_tmerc_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "p3d_proj_tmerc": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "p3d_proj_smooth_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "p3d_tide_predict_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3d_tide_predict": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1544,6 +1548,41 @@ def proj_smooth(padded, w, device=0):
     finally:
         din.free()
         dout.free()
+
+
+# ---- step 6: harmonic tide prediction (include/p3d.h, p3d_tide.hip) ------------------------------------------------
+def _tide_small(grid, ids, nc):
+    grid, ids = np.ascontiguousarray(grid, dtype=np.float64), np.ascontiguousarray(ids, dtype=np.int32)
+    if grid.shape != (4,):
+        raise ValueError("the grid numbers are (lon0, dlon, lat0, dlat)")
+    if ids.shape != (nc,):
+        raise ValueError(f"{nc} table planes but constituent ids of shape {ids.shape}")
+    return grid, ids
+
+
+def tide_predict_dev(lon, lat, t, n, hre, him, wet, nc, nxs, nys, grid, ids, out, device=0):
+    """p3d_tide_predict_dev: ``lon``, ``lat``, ``t`` (n float64 each), the tables ``hre`` / ``him`` (int32 [nc][nxs][nys]) and ``wet`` (uint8
+    [nxs][nys]) and the result ``out`` (n float64) are device pointers; ``grid`` = (lon0, dlon, lat0, dlat) and ``ids`` [nc] are HOST arrays."""
+    grid, ids = _tide_small(grid, ids, int(nc))
+    check(lib().p3d_tide_predict_dev(int(device), lon, lat, t, int(n), hre, him, wet, int(nc), int(nxs), int(nys), _ptr(grid), _ptr(ids), out))
+
+
+def tide_predict(lon, lat, t, hre, him, wet, grid, ids, device=0):
+    """Tide in metres at host points (p3d_tide_predict): ``lon`` / ``lat`` in degrees (longitudes on the subset's axis), ``t`` in seconds since
+    1992-01-01T00:00:00, the subset tables ``hre`` / ``him`` int32 [nc][nxs][nys] in millimetres and ``wet`` uint8 [nxs][nys], ``grid`` =
+    (lon0, dlon, lat0, dlat), ``ids`` [nc] constituent ids (positions in ``functions.tide_model.CONSTITUENTS``).  Returns float64 of the points' shape."""
+    lon, lat, t = (np.ascontiguousarray(v, dtype=np.float64) for v in (lon, lat, t))
+    if not lon.shape == lat.shape == t.shape:
+        raise ValueError(f"lon {lon.shape}, lat {lat.shape} and t {t.shape} differ in shape")
+    hre, him, wet = np.ascontiguousarray(hre, dtype=np.int32), np.ascontiguousarray(him, dtype=np.int32), np.ascontiguousarray(wet, dtype=np.uint8)
+    if hre.ndim != 3 or him.shape != hre.shape or wet.shape != hre.shape[1:]:
+        raise ValueError(f"tables are hre / him [nc][nxs][nys] and wet [nxs][nys], got {hre.shape}, {him.shape}, {wet.shape}")
+    nc, nxs, nys = hre.shape
+    grid, ids = _tide_small(grid, ids, nc)
+    out = np.empty_like(lon)
+    check(lib().p3d_tide_predict(int(device), _ptr(lon), _ptr(lat), _ptr(t), lon.size, _ptr(hre), _ptr(him), _ptr(wet), nc, nxs, nys, _ptr(grid),
+                                 _ptr(ids), _ptr(out)))
+    return out
 
 
 # ---- step 7: mistie correction (include/p3d.h, p3d_mistie.hip) ---------------------------------------------------

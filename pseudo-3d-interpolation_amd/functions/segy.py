@@ -8,7 +8,8 @@ and samples are read without copying the file; samples are converted to float32 
 Trace header fields (1-based byte positions, the ones step 10 scrapes): 1 TRACE_SEQUENCE_LINE, 5 TRACE_SEQUENCE_FILE, 9 FieldRecord,
 71 SourceGroupScalar, 73 SourceX, 77 SourceY, 109 DelayRecordingTime, 115 TRACE_SAMPLE_COUNT, 117 TRACE_SAMPLE_INTERVAL (microseconds); the ones
 step 5 reads and writes: 61 SourceWaterDepth, 69 ElevationScalar, 103 TotalStaticApplied, 233 UnassignedInt1, 237 UnassignedInt2; the ones step 2
-adds: 81 GroupX, 85 GroupY, 89 CoordinateUnits, 181 CDP_X, 185 CDP_Y.  Step 4 writes a copy of a file with another trace length (`write_resized`)."""
+adds: 81 GroupX, 85 GroupY, 89 CoordinateUnits, 181 CDP_X, 185 CDP_Y; the recording time step 6 reads: 157 YearDataRecorded, 159 DayOfYear, 161 HourOfDay,
+163 MinuteOfHour, 165 SecondOfMinute.  Step 4 writes a copy of a file with another trace length (`write_resized`)."""
 import os
 
 import numpy as np
@@ -32,6 +33,11 @@ TRACE_FIELDS = {
     'DelayRecordingTime': (109, '>i2'),
     'TRACE_SAMPLE_COUNT': (115, '>u2'),
     'TRACE_SAMPLE_INTERVAL': (117, '>u2'),
+    'YearDataRecorded': (157, '>i2'),
+    'DayOfYear': (159, '>i2'),
+    'HourOfDay': (161, '>i2'),
+    'MinuteOfHour': (163, '>i2'),
+    'SecondOfMinute': (165, '>i2'),
     'CDP_X': (181, '>i4'),
     'CDP_Y': (185, '>i4'),
     'UnassignedInt1': (233, '>i4'),

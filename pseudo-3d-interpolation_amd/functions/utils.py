@@ -1,4 +1,4 @@
-"""Small utilities mirrored from pseudo_3D_interpolation/functions/utils.py (only what steps 11-15 use)."""
+"""Small utilities mirrored from pseudo_3D_interpolation/functions/utils.py (only what the steps of this package use)."""
 from functools import partial
 
 import numpy as np
@@ -52,3 +52,27 @@ def convert_twt(twt, unit_in: str, unit_out: str):
     fact_in, fact_out = units[unit_in], units[unit_out]
     factor = fact_in / fact_out if fact_in > fact_out else fact_in * fact_out
     return twt * factor
+
+
+def dt_seconds(dt, units):
+    """``dt`` in seconds; 'ns' divides by 1e-6 as the reference does."""
+    if units == 'ms':
+        return dt / 1000
+    if units == 'ns':
+        return dt / 1e-6
+    return dt
+
+
+def depth2twt(depth, v=1500):
+    """Depth (m) -> two-way travel time (s) at sound velocity ``v`` (functions/utils.py:304-306)."""
+    return depth / (v / 2)
+
+
+def twt2samples(twt, dt, units='s'):
+    """Two-way travel time (s) -> samples of ``dt`` [``units``] (functions/utils.py:319-328)."""
+    return twt / dt_seconds(dt, units)
+
+
+def depth2samples(depth, dt, v=1500, units='s'):
+    """Depth (m) -> samples of ``dt`` [``units``] (functions/utils.py:336-347)."""
+    return twt2samples(depth2twt(depth, v=v), dt_seconds(dt, units))
