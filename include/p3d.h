@@ -576,6 +576,31 @@ int p3d_tide_predict_dev(int device, const double* lon_dev, const double* lat_de
 int p3d_tide_predict(int device, const double* lon, const double* lat, const double* t, size_t n, const int* hre, const int* him, const unsigned char* wet,
                      int nc, int nxs, int nys, const double* grid, const int* ids, double* tide);
 
+/* ---- steps 9 and 16: SEG-Y <-> float32 sections (p3d_segy.hip; the reference's cnv_segy2netcdf.py / cube_cnv_netcdf2segy_3D.py, which use segysak) ----
+ * A record is a 240-byte trace header followed by ns samples, all big-endian; ns = 1 ... 65535.  The sample conversions are bit-identical to
+ * functions/segy.py (ieee2ibm: mantissa to nearest, ties to even; +-0 and NaN -> 0, +-Inf -> 0x7FFFFFFF / 0xFFFFFFFF; ibm2ieee: NumPy's cast of the
+ * exact double, so subnormals are rounded to nearest-even, larger magnitudes become +-inf and a zero mantissa keeps its sign).
+ *   encode: section float32, trace-major [ntr][ns] or slice-major [ns][ntr] (the ('twt', 'iline', 'xline') cube, ntr = nil nxl) -> ntr records of
+ *           240 + 4 ns bytes in format 1 (IBM) or 5 (IEEE).  Every header is the 240-byte template overlaid with the columns: column c puts
+ *           values[c][x] (int32) as a big-endian word of columns[c][1] = 2 or 4 bytes (the low 16 bits for 2) at byte offset columns[c][0] of
+ *           trace x's header.  columns: HOST, [ncol][2], ncol <= P3D_SEGY_MAX_COLUMNS; values: [ncol][ntr].
+ *   decode: records of 240 + ns bytes(fmt) bytes, fmt 1, 2 (int32), 3 (int16), 5, 8 (int8) -> samples float32 [ntr][ns] (integers converted as NumPy's
+ *           astype(float32) converts them) and words[k][x] = the header word of fields[k] = {byte offset, width 2 | 4, signed != 0} of trace x, as
+ *           int32 (an unsigned 4-byte word keeps its bit pattern).  fields: HOST, [nf][3], nf <= P3D_SEGY_MAX_COLUMNS; words: [nf][ntr].
+ * P3D_ERR_INVALID before anything is launched: ns outside 1 ... 65535, another format or layout, more than 16 columns / fields, a width other than
+ * 2 or 4, a column / field that leaves the 240 bytes or overlaps another.  ntr = 0: nothing is done.
+ * Entries with the _dev suffix: the section, the records, the template, values and words DEVICE; section and records start at 16-byte boundaries
+ * and do not overlap.  Entries without it: all of them HOST. */
+#define P3D_SEGY_MAX_COLUMNS 16
+#define P3D_SEGY_TRACE_MAJOR 0
+#define P3D_SEGY_SLICE_MAJOR 1
+int p3d_segy_encode_dev(int device, const float* section_dev, int ntr, int ns, int layout, int fmt, const unsigned char* template_dev, const int* columns,
+                        int ncol, const int* values_dev, unsigned char* records_dev);
+int p3d_segy_encode(int device, const float* section, int ntr, int ns, int layout, int fmt, const unsigned char* tmpl, const int* columns, int ncol,
+                    const int* values, unsigned char* records);
+int p3d_segy_decode_dev(int device, const unsigned char* records_dev, int ntr, int ns, int fmt, const int* fields, int nf, float* samples_dev, int* words_dev);
+int p3d_segy_decode(int device, const unsigned char* records, int ntr, int ns, int fmt, const int* fields, int nf, float* samples, int* words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,10 @@ PROTOTYPES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "p3d_tide_predict": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3d_segy_encode_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_segy_encode": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_segy_decode_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_segy_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1496,6 +1500,67 @@ def delrt_windows(subsets, n_samples, device=0):
     peak_idx, peak_val, maxima = np.empty(m, np.int32), np.empty(m, np.float32), np.empty((m, width), np.float32)
     check(lib().p3d_delrt_windows(int(device), _ptr(subsets), m, ns, n_traces, n_samples, _ptr(peak_idx), _ptr(peak_val), _ptr(maxima)))
     return peak_idx, peak_val, maxima
+
+
+# ---- steps 9 and 16: SEG-Y records <-> float32 sections (include/p3d.h, p3d_segy.hip) -------------------------------
+SEGY_LAYOUT = {"trace": 0, "slice": 1}
+SEGY_SAMPLE_BYTES = {1: 4, 2: 4, 3: 2, 5: 4, 8: 1}
+
+
+def _segy_table(rows, width):
+    """A small HOST table of header words as int32 [n][width]; an empty one for no rows."""
+    table = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, width)
+    return table, table.shape[0]
+
+
+def segy_encode_dev(section, ntr, ns, layout, fmt, template, columns, values, records, device=0):
+    """p3d_segy_encode_dev on device pointers: ``section`` float32 [ntr][ns] (``layout`` 'trace') or [ns][ntr] ('slice'), ``template`` 240 bytes,
+    ``values`` int32 [ncol][ntr], ``records`` ntr x (240 + 4 ns) bytes; ``columns`` a HOST table of (byte offset, width 2 | 4)."""
+    columns, ncol = _segy_table(columns, 2)
+    check(lib().p3d_segy_encode_dev(int(device), section, int(ntr), int(ns), SEGY_LAYOUT[layout], int(fmt), template, _ptr(columns), ncol, values, records))
+
+
+def segy_encode(section, layout, fmt, template, columns, values, device=0):
+    """SEG-Y records uint8 [ntr][240 + 4 ns] of a host section, float32 [ntr][ns] (``layout`` 'trace') or [ns][ntr] ('slice'), in sample format 1
+    (IBM) or 5 (IEEE): every header is ``template`` (240 bytes) overlaid with ``values[c][x]`` as a big-endian word of ``columns[c]`` = (byte
+    offset, width 2 | 4) (p3d_segy_encode)."""
+    section = np.ascontiguousarray(section, dtype=np.float32)
+    if section.ndim != 2:
+        raise ValueError("the section is [ntraces][nsamples] or [nsamples][ntraces]")
+    ntr, ns = section.shape if SEGY_LAYOUT[layout] == 0 else section.shape[::-1]
+    template = np.ascontiguousarray(template, dtype=np.uint8)
+    if template.shape != (240,):
+        raise ValueError("the header template holds 240 bytes")
+    columns, ncol = _segy_table(columns, 2)
+    values = np.ascontiguousarray(values, dtype=np.int32)
+    if values.size != ncol * ntr:
+        raise ValueError(f"{ncol} columns of {ntr} traces but {values.size} values")
+    records = np.empty((ntr, 240 + 4 * max(ns, 0)), np.uint8)
+    check(lib().p3d_segy_encode(int(device), _ptr(section), ntr, ns, SEGY_LAYOUT[layout], int(fmt), _ptr(template), _ptr(columns), ncol, _ptr(values),
+                                _ptr(records)))
+    return records
+
+
+def segy_decode_dev(records, ntr, ns, fmt, fields, samples, words, device=0):
+    """p3d_segy_decode_dev on device pointers: ``records`` ntr x (240 + ns x bytes(fmt)) bytes, ``samples`` float32 [ntr][ns], ``words`` int32
+    [nfields][ntr]; ``fields`` a HOST table of (byte offset, width 2 | 4, signed)."""
+    fields, nf = _segy_table(fields, 3)
+    check(lib().p3d_segy_decode_dev(int(device), records, int(ntr), int(ns), int(fmt), _ptr(fields), nf, samples, words))
+
+
+def segy_decode(records, ns, fmt, fields, device=0):
+    """``(samples float32 [ntr][ns], words int32 [nfields][ntr])`` of host records uint8 [ntr][240 + ns x bytes(fmt)] in sample format 1, 2, 3, 5
+    or 8; ``fields``: (byte offset, width 2 | 4, signed) of the header words to scrape (p3d_segy_decode)."""
+    records = np.ascontiguousarray(records, dtype=np.uint8)
+    ns, fmt = int(ns), int(fmt)
+    reclen = 240 + max(ns, 0) * SEGY_SAMPLE_BYTES.get(fmt, 4)
+    if records.ndim != 2 or records.shape[1] != reclen:
+        raise ValueError(f"records are [ntraces][{reclen}] bytes for {ns} samples of format {fmt}")
+    ntr = records.shape[0]
+    fields, nf = _segy_table(fields, 3)
+    samples, words = np.empty((ntr, max(ns, 0)), np.float32), np.empty((nf, ntr), np.int32)
+    check(lib().p3d_segy_decode(int(device), _ptr(records), ntr, ns, fmt, _ptr(fields), nf, _ptr(samples), _ptr(words)))
+    return samples, words
 
 
 # ---- step 2: reprojection of header coordinates (include/p3d.h, p3d_proj.hip) --------------------------------------

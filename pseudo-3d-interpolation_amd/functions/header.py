@@ -1,9 +1,12 @@
-"""Textual-header helpers that step 8 needs (the reference keeps them in functions/header.py), on plain files with the standard library only.
+"""Textual-header helpers that step 8 needs (the reference keeps them in functions/header.py), on plain files with the standard library; and
+the coordinate-scalar rule of step 16 (NumPy only for reading the first coordinate).
 
 A SEG-Y textual header is 3200 characters: 40 cards of 80, each opening with a 3-character label ('C 1' ... 'C40').  Processing steps are
 logged as cards of the form ' YYYY-MM-DD: STEP' below a centred title card '***** PROCESSING WORKFLOW *****' (card 25 unless it exists elsewhere)."""
 import datetime
 import warnings
+
+import numpy as np
 
 CARDS, WIDTH, LABEL = 40, 80, 3
 TITLE = '***** PROCESSING WORKFLOW *****'
@@ -100,3 +103,25 @@ def write_textual_header(path, txt, **kwargs_segy):
         codec = _codec(fh.read(CARDS * WIDTH))
         fh.seek(0)
         fh.write(flat.encode(codec, 'replace'))
+
+
+def check_coordinate_scalar(coord_scalar, xcoords=None, ycoords=None):
+    """The coordinate scalar for header word 71 and the factor the coordinates are multiplied by before they are stored, ``(scalar, factor)``.
+
+    A negative scalar means "divide on reading": factor = |scalar|; a positive one "multiply on reading": factor = 1 / scalar; 0 and ``None``
+    give (0, 1).  'auto' fills the ten digits of a 32-bit word: with n characters in front of the decimal point of the first x or y coordinate
+    as ``str`` prints it (the longer of the two; a minus sign counts, as in the reference), factor = 10^(9 - n), scalar = -factor, or
+    int(1 / factor) where the factor is 1 or less."""
+    if coord_scalar is None:
+        coord_scalar = 0
+    if isinstance(coord_scalar, str):
+        if coord_scalar != 'auto':
+            raise ValueError(f"coordinate scalar {coord_scalar!r}: an integer or 'auto'")
+        ndigits = max(str(np.asarray(c).flat[0]).find('.') for c in (xcoords, ycoords))
+        factor = 10 ** (9 - ndigits)
+        return (-factor if factor > 1 else int(1 / factor)), factor
+    if coord_scalar > 0:
+        return coord_scalar, 1 / abs(coord_scalar)
+    if coord_scalar < 0:
+        return coord_scalar, abs(coord_scalar)
+    return coord_scalar, 1
