@@ -20,9 +20,9 @@ import numpy as np
 
 from . import cube_io
 from .cube_io import Cube
-from .despiking_2D_segy import input_files
 from .functions.backends import h5py_enabled
 from .functions.segy import scaled_coordinates
+from .functions.segy_cli import input_files
 from .functions.segy_gpu import read_segy_gpu
 from .functions.utils import xprint
 

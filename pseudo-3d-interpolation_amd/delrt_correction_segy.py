@@ -13,19 +13,16 @@ copy or in place (the reference writes it only with ``--inplace``); and it is wr
 message names that trace, yet it writes the header of the first trace behind the change -- the two differ for an offset trace).
 """
 import argparse
-import datetime
 import os
 import sys
-from contextlib import redirect_stdout
 from functools import partial
-from shutil import copy2
 
 import numpy as np
 
-from .despiking_2D_segy import clean_log_file, header_words, input_files
+from .functions import segy_cli
 from .functions.delrt import correct_delay_changes, correct_single_trace_DelayRecordingTime, delay_changes  # noqa: F401
 from .functions.header import add_processing_info_header, get_textual_header, write_textual_header
-from .functions.segy import TRACE_FIELDS, SegyFile, update_headers
+from .functions.segy import SegyFile, header_words, write_header_words
 from .functions.utils import xprint
 
 MSG_SKIPPED = 'Skipped: Identical "DelayRecordingTime" for whole SEG-Y file'
@@ -63,52 +60,6 @@ def check_varying_DelayRecordingTimes(path, byte_delay=109):
     return len(np.unique(header_words(SegyFile(path), byte_delay))) > 1
 
 
-def write_header_words(path, byte, rows, values):
-    """Set the trace-header word at 1-based ``byte`` of traces ``rows`` to ``values``: with the width of the reader's named field that starts
-    there, else as a big-endian int16 (the rule `header_words` reads by)."""
-    segy = SegyFile(path)
-    ntr, size = segy.ntraces, segy._dtype.itemsize
-    for name, (b, _) in TRACE_FIELDS.items():
-        if b == byte:
-            words = segy.header(name)
-            del segy
-            words[np.asarray(rows)] = values
-            return update_headers(path, {name: words})
-    del segy
-    info = np.iinfo(np.int16)
-    if np.min(values) < info.min or np.max(values) > info.max:
-        raise OverflowError(f'byte {byte}: values outside the range of a 16-bit header word')
-    raw = np.memmap(path, np.uint8, 'r+')
-    start = raw.size - ntr * size
-    packed = np.asarray(values).astype('>i2').reshape(-1, 1).view(np.uint8)
-    raw[start:].reshape(ntr, size)[np.asarray(rows), byte - 1:byte + 1] = packed
-    raw.flush()
-    del raw
-    return path
-
-
-def output_target(in_path, args, say):
-    """Path of the file that is edited; the copy is made here."""
-    folder, name = os.path.split(in_path)
-    stem, ext = os.path.splitext(name)
-    if args.inplace:                                            # supersedes any --output_dir
-        say('Updating SEG-Y inplace', kind='warning')
-        return in_path
-    if args.output_dir is None:
-        say('Creating copy of file in INPUT directory:\n', folder, kind='info')
-    elif os.path.isdir(args.output_dir):
-        say('Creating copy of file in OUTPUT directory:\n', args.output_dir, kind='info')
-        folder = args.output_dir
-    else:
-        raise FileNotFoundError(f'The output directory > {args.output_dir} < does not exist')
-    target = os.path.join(folder, f"{stem}_{'delrt' if args.txt_suffix is None else args.txt_suffix}{ext}")
-    if os.path.isfile(target):
-        say('Output file already exists and will be removed!', kind='warning')
-        os.remove(target)
-    copy2(in_path, target)
-    return target
-
-
 def wrapper_delrt_correction_segy(in_path, args):
     """Correct the DelayRecordingTime of one SEG-Y file.  Returns False for a file with one delay (nothing is written), else the list of
     corrections ``[(idx, trace, old, new)]`` (possibly empty) that were written to the output file."""
@@ -116,7 +67,7 @@ def wrapper_delrt_correction_segy(in_path, args):
     say(f'Processing file < {os.path.basename(in_path)} >', kind='info')
     if not check_varying_DelayRecordingTimes(in_path, args.byte_delay):
         return False
-    path = output_target(in_path, args, say)
+    path, _, _ = segy_cli.copied_target(in_path, args, 'delrt', say)
 
     segy = SegyFile(path)
     delrt = header_words(segy, args.byte_delay)
@@ -137,28 +88,9 @@ def wrapper_delrt_correction_segy(in_path, args):
 
 
 def main(argv=sys.argv):  # noqa
-    stamp = datetime.datetime.now().isoformat(timespec='seconds').replace(':', '')
-    script = os.path.splitext(os.path.basename(__file__))[0]
     args = define_input_args().parse_args(argv[1:])
-
-    files, folder, single = input_files(args.input_path, args)
-    if single:
-        if wrapper_delrt_correction_segy(files[0], args) is False:
-            xprint(MSG_SKIPPED, kind='info', verbosity=args.verbose)
-        sys.exit()
-    if not files:
-        sys.exit('[INFO]    No input files to process. Exit process.')
-    log_path = os.path.join(folder, f'{stamp}_{script}.log')
-    nprocessed = 0
-    with open(log_path, 'w', newline='\n') as log, redirect_stdout(log):
-        xprint(f'Processing total of < {len(files)} > files', kind='info', verbosity=args.verbose)
-        for one in files:
-            if wrapper_delrt_correction_segy(one, args) is False:
-                xprint(MSG_SKIPPED, kind='info', verbosity=args.verbose)
-                continue
-            nprocessed += 1
-        xprint(f'Fixed a total of < {nprocessed} > out of < {len(files)} > files', kind='info', verbosity=args.verbose)
-    clean_log_file(log_path)
+    segy_cli.run(__file__, args, lambda path: wrapper_delrt_correction_segy(path, args), skipped=MSG_SKIPPED,
+                 summary='Fixed a total of < {done} > out of < {total} > files', empty='[INFO]    ' + segy_cli.MSG_NO_FILES)
 
 
 if __name__ == '__main__':

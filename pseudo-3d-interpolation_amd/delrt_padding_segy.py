@@ -10,18 +10,16 @@ recognises a padded file by.  Flags, defaults, the three kinds of input (a file,
 ``.txt`` list), the log file and the "skipped" message for a file with one delay are the reference's.
 """
 import argparse
-import datetime
 import os
 import sys
-from contextlib import redirect_stdout
 from functools import partial
 
 import numpy as np
 
-from .despiking_2D_segy import clean_log_file, header_words, input_files
+from .functions import segy_cli
 from .functions.delrt import pad_trace_data
 from .functions.header import add_processing_info_header, get_textual_header, write_textual_header
-from .functions.segy import TRACE_FIELDS, SegyFile, write_resized
+from .functions.segy import TRACE_FIELDS, SegyFile, header_words, write_resized
 from .functions.utils import xprint
 
 MSG_SKIPPED = 'Continuous "DelayRecordingTime" for whole SEG-Y file --> skipped!'
@@ -49,27 +47,13 @@ def define_input_args():  # noqa
 # fmt: on
 
 
-def output_path(in_path, args, say):
-    folder, name = os.path.split(in_path)
-    stem, ext = os.path.splitext(name)
-    if args.output_dir is None:
-        say('Creating copy of file in INPUT directory:\n', folder, kind='info')
-    elif os.path.isdir(args.output_dir):
-        say('Creating copy of file in OUTPUT directory:\n', args.output_dir, kind='info')
-        folder = args.output_dir
-    else:
-        raise FileNotFoundError(f'The output directory > {args.output_dir} < does not exist')
-    return os.path.join(folder, f"{stem}_{'pad' if args.txt_suffix is None else args.txt_suffix}{ext}")
-
-
 def wrapper_delrt_padding_segy(in_path, args):
     """Pad one SEG-Y file.  Returns False for a file with one delay (nothing is written), else the path of the padded file."""
     say = partial(xprint, verbosity=args.verbose)
     say(f'Processing file < {os.path.basename(in_path)} >', kind='info')
-    target = output_path(in_path, args, say)
-    if os.path.isfile(target):
-        say('Output file already exists and will be removed!', kind='warning')
-        os.remove(target)
+    target, _, _ = segy_cli.output_target(in_path, args, 'pad')
+    segy_cli.say_target(in_path, target, args, say)
+    segy_cli.remove_existing(target, say)                                            # the padded file is written anew, not copied
 
     segy = SegyFile(in_path)
     recording_delays = header_words(segy, args.byte_delay)
@@ -93,28 +77,9 @@ def wrapper_delrt_padding_segy(in_path, args):
 
 
 def main(argv=sys.argv):  # noqa
-    stamp = datetime.datetime.now().isoformat(timespec='seconds').replace(':', '')
-    script = os.path.splitext(os.path.basename(__file__))[0]
     args = define_input_args().parse_args(argv[1:])
-
-    files, folder, single = input_files(args.input_path, args)
-    if single:
-        if wrapper_delrt_padding_segy(files[0], args) is False:
-            xprint(MSG_SKIPPED, kind='info', verbosity=args.verbose)
-        sys.exit()
-    if not files:
-        sys.exit('No input files to process. Exit process.')
-    log_path = os.path.join(folder, f'{stamp}_{script}.log')
-    nprocessed = 0
-    with open(log_path, 'w', newline='\n') as log, redirect_stdout(log):
-        xprint(f'Processing total of < {len(files)} > files', kind='info', verbosity=args.verbose)
-        for one in files:
-            if wrapper_delrt_padding_segy(one, args) is False:
-                xprint(MSG_SKIPPED, kind='info', verbosity=args.verbose)
-                continue
-            nprocessed += 1
-        xprint(f'Padded a total of < {nprocessed} > out of < {len(files)} > files', kind='info', verbosity=args.verbose)
-    clean_log_file(log_path)
+    segy_cli.run(__file__, args, lambda path: wrapper_delrt_padding_segy(path, args), skipped=MSG_SKIPPED,
+                 summary='Padded a total of < {done} > out of < {total} > files')
 
 
 if __name__ == '__main__':

@@ -13,21 +13,17 @@ traces replaces its own trace; with ``--use_delay`` a split narrower than the tr
 the QC figures of the reference are not produced.
 """
 import argparse
-import datetime
-import glob
 import os
-import re
 import sys
-from contextlib import redirect_stdout
 from functools import partial
-from shutil import copy2
 
 import numpy as np
 import yaml
 
+from .functions import segy_cli
 from .functions.despike import despike_2D
 from .functions.header import add_processing_info_header, get_textual_header, write_textual_header
-from .functions.segy import TRACE_FIELDS, SegyFile, update_samples
+from .functions.segy import SegyFile, header_words, update_samples
 from .functions.utils import xprint
 
 
@@ -57,47 +53,10 @@ def define_input_args():  # noqa
 # fmt: on
 
 
-ANSI_COLOUR = re.compile(r'\x1b\[[0-9;]*m')
 MSG_OVERLAP = '[ERROR]    Please set window overlap to a reasonable value [0-99].'
 MSG_THRESHOLD = '[ERROR]    Threshold factor must be larger than zero.'
 MSG_TOO_FEW = 'Input SEG-Y contains too less traces for despiking ---> skipped file!'
 MSG_NOTHING = '*** No spikes removed! Consider adjusting the input parameters. ***'
-
-
-def clean_log_file(path_log, newline='\n'):
-    """Strip the terminal colour codes from a log file."""
-    with open(path_log) as fh:
-        text = fh.read()
-    with open(path_log, 'w', newline=newline) as fh:
-        fh.write(ANSI_COLOUR.sub('', text))
-
-
-def output_path(in_path, args):
-    """Where the despiked copy of ``in_path`` goes (the file itself with ``--inplace``, which supersedes ``--output_dir``)."""
-    if args.inplace:
-        return in_path
-    folder, name = os.path.split(in_path)
-    if args.output_dir is not None:
-        if not os.path.isdir(args.output_dir):
-            raise FileNotFoundError(f'The output directory > {args.output_dir} < does not exist')
-        folder = args.output_dir
-    stem, ext = os.path.splitext(name)
-    tag = 'despk' if args.txt_suffix is None else args.txt_suffix
-    return os.path.join(folder, f'{stem}_{tag}{ext}')
-
-
-def header_words(segy, byte):
-    """The trace-header word at 1-based ``byte`` of every trace.  A byte that starts one of the reader's named fields (``TRACE_FIELDS``) is
-    read with that field's width; any other byte is read as a big-endian int16, the width of the delay time and its neighbours."""
-    for name, (b, _) in TRACE_FIELDS.items():
-        if b == byte:
-            return segy.header(name)
-    if not 1 <= byte <= 239:
-        raise ValueError(f'--byte_delay {byte} is outside the 240-byte trace header')
-    raw = np.memmap(segy.path, np.uint8, 'r')
-    start = raw.size - segy.ntraces * segy._dtype.itemsize
-    rows = raw[start:].reshape(segy.ntraces, segy._dtype.itemsize)[:, byte - 1:byte + 1]
-    return np.ascontiguousarray(rows).view('>i2').ravel().astype(np.int64)
 
 
 def wrapper_despiking_2D_segy(in_path, args):
@@ -105,15 +64,12 @@ def wrapper_despiking_2D_segy(in_path, args):
     than the trace window."""
     say = partial(xprint, verbosity=args.verbose)
     say(f'Processing file < {os.path.basename(in_path)} >', kind='info')
-    target = output_path(in_path, args)
+    target, _, _ = segy_cli.output_target(in_path, args, 'despk')
     if target == in_path:
         say('Updating SEG-Y inplace', kind='warning')
     else:
         say('Creating copy of file in directory:\n', os.path.dirname(target), kind='info')
-        if os.path.exists(target):
-            say('Output file already exists and will be removed!', kind='warning')
-            os.unlink(target)
-        copy2(in_path, target)
+    segy_cli.copy_to_target(in_path, target, say)
 
     segy = SegyFile(target)
     if segy.ntraces < args.window_traces:
@@ -150,23 +106,6 @@ def despike_file(in_path, args):
     return False
 
 
-def input_files(in_path, args):
-    """(files, folder, single): the files named by a SEG-Y file, a directory (``*{filename_suffix}.{suffix}``) or a ``.txt`` list (names
-    relative to the list), the folder that takes the log, and whether the input was one SEG-Y file."""
-    ext = os.path.splitext(in_path)[1]
-    if os.path.isdir(in_path):
-        glob_pattern = '*' + (args.filename_suffix or '') + '.' + (args.suffix if args.suffix is not None else 'sgy')
-        return sorted(glob.glob(os.path.join(in_path, glob_pattern))), in_path, False
-    if not os.path.isfile(in_path):
-        raise FileNotFoundError('Invalid input file')
-    folder = os.path.dirname(in_path)
-    if ext != '.txt':
-        return [in_path], folder, True
-    with open(in_path) as fh:
-        entries = [ln.strip() for ln in fh if ln.strip()]
-    return [e if os.path.isabs(e) else os.path.join(folder, e) for e in entries], folder, False
-
-
 def main(argv=sys.argv):  # noqa
     args = define_input_args().parse_args(argv[1:])
     xprint(args, kind='debug', verbosity=args.verbose)
@@ -175,8 +114,7 @@ def main(argv=sys.argv):  # noqa
     if args.threshold_factor is None or args.threshold_factor <= 0:
         sys.exit(MSG_THRESHOLD)
 
-    stamp = datetime.datetime.now().strftime('%Y-%m-%dT%H%M%S')
-    script = os.path.splitext(os.path.basename(__file__))[0]
+    stamp, script = segy_cli.time_stamp(), segy_cli.script_name(__file__)
     in_path = args.input_path
     folder = in_path if os.path.splitext(in_path)[1] == '' else os.path.dirname(in_path)
     if args.verbose >= 1:
@@ -185,18 +123,7 @@ def main(argv=sys.argv):  # noqa
         with open(yml, 'w', newline='\n') as fh:
             yaml.safe_dump(vars(args), fh)
 
-    files, folder, single = input_files(in_path, args)
-    if single:
-        despike_file(files[0], args)
-        sys.exit()
-    if not files:
-        sys.exit('No input files to process. Exit process.')
-    log_path = os.path.join(folder, f'{stamp}_{script}.log')
-    with open(log_path, 'w', newline='\n') as log, redirect_stdout(log):
-        xprint(f'Processing total of < {len(files)} > files', kind='info', verbosity=args.verbose)
-        for one in files:
-            despike_file(one, args)
-    clean_log_file(log_path)
+    segy_cli.run(__file__, args, lambda path: despike_file(path, args), stamp=stamp)     # the log shares the stamp of the .yml
 
 
 if __name__ == '__main__':

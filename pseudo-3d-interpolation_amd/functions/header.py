@@ -1,5 +1,6 @@
 """Textual-header helpers that step 8 needs (the reference keeps them in functions/header.py), on plain files with the standard library; and
-the coordinate-scalar rule of step 16 (NumPy only for reading the first coordinate).
+the coordinate-scalar rule of step 16 (NumPy only for reading the first coordinate); and the scaling of header coordinates that steps 2 and 6
+share (`scale_coordinates`, `unscale_coordinates`, as in the reference's functions/header.py).
 
 A SEG-Y textual header is 3200 characters: 40 cards of 80, each opening with a 3-character label ('C 1' ... 'C40').  Processing steps are
 logged as cards of the form ' YYYY-MM-DD: STEP' below a centred title card '***** PROCESSING WORKFLOW *****' (card 25 unless it exists elsewhere)."""
@@ -8,9 +9,16 @@ import warnings
 
 import numpy as np
 
+from .segy import field_at
+
 CARDS, WIDTH, LABEL = 40, 80, 3
 TITLE = '***** PROCESSING WORKFLOW *****'
 FULL = 'SEG-Y textual header is already full. Adding more information is not possible.'
+# 1-based bytes of the x / y words the step CLIs' `--src_coords` / `--dst_coords` choose among
+TRACE_HEADER_COORDS = {'source': (73, 77), 'CDP': (181, 185), 'group': (81, 85)}
+COORDS = ['source', 'CDP', 'group']
+ARC_SECONDS = 3600000
+MSG_FORCED = 'Forced source CRS to be geographic (WGS84 - EPSG:4326)!'
 
 
 def _cards(txt):
@@ -125,3 +133,37 @@ def check_coordinate_scalar(coord_scalar, xcoords=None, ycoords=None):
     if coord_scalar < 0:
         return coord_scalar, abs(coord_scalar)
     return coord_scalar, 1
+
+
+def scale_coordinates(segy, src_coords_bytes=(73, 77)):
+    """(x, y, CoordinateUnits): the header coordinates at ``src_coords_bytes`` in their real unit.  The FIRST trace decides for all: units 1
+    (length) apply its ``SourceGroupScalar`` (negative: divide by its magnitude, positive: multiply, 0: as stored), units 2 (seconds of arc)
+    divide by 3 600 000; units 3 and 4 are not implemented (reference: functions/header.py ``scale_coordinates``).  This is reprojection's rule;
+    `functions.segy.scaled_coordinates` is binning's, where a scalar of 0 gives 0 and the units are not looked at."""
+    units = int(segy.header('CoordinateUnits')[0])
+    x, y = segy.header(field_at(src_coords_bytes[0])), segy.header(field_at(src_coords_bytes[1]))
+    if units == 1:
+        scalar = int(segy.header('SourceGroupScalar')[0])
+        if scalar < 0:
+            x, y = x / np.abs(scalar), y / np.abs(scalar)
+        elif scalar > 0:
+            x, y = x * np.abs(scalar), y * np.abs(scalar)
+    elif units == 2:
+        x, y = x / ARC_SECONDS, y / ARC_SECONDS
+    elif units == 3:
+        raise NotImplementedError('Functionality to convert DD data is not implemented.')
+    elif units == 4:
+        raise NotImplementedError('Functionality to convert DMS data is not implemented.')
+    return x, y, units
+
+
+def unscale_coordinates(x, y, scale_factor=-100):
+    """Coordinates in metres as the integers of a header with scalar ``scale_factor``: rounded ``v * |scalar|`` for a negative scalar,
+    rounded ``v / |scalar|`` for a positive one, rounded ``v`` for 0 (reference: functions/header.py ``unscale_coordinates``, units 1).  The
+    inverse of `scale_coordinates` (reprojection's rule), not of `functions.segy.scaled_coordinates` (binning's)."""
+    x, y = np.asarray(x), np.asarray(y)
+    if scale_factor < 0:
+        x, y = x * np.abs(scale_factor), y * np.abs(scale_factor)
+    elif scale_factor > 0:
+        x, y = x / np.abs(scale_factor), y / np.abs(scale_factor)
+    return np.around(x, 0).astype(np.int64), np.around(y, 0).astype(np.int64)

@@ -154,9 +154,35 @@ class SegyFile:
         return np.asarray(raw).astype(np.float32)
 
 
+def field_at(byte, missing_ok=False):
+    """Name of the reader's trace-header field (``TRACE_FIELDS``) that starts at 1-based ``byte``; without one a ``KeyError``, or ``None``
+    with ``missing_ok``."""
+    for name, (b, _) in TRACE_FIELDS.items():
+        if b == byte:
+            return name
+    if missing_ok:
+        return None
+    raise KeyError(f'no trace-header field at byte {byte}')
+
+
+def header_words(segy, byte):
+    """The trace-header word at 1-based ``byte`` of every trace.  A byte that starts one of the reader's named fields (``TRACE_FIELDS``) is
+    read with that field's width; any other byte is read as a big-endian int16, the width of the delay time and its neighbours."""
+    name = field_at(byte, missing_ok=True)
+    if name is not None:
+        return segy.header(name)
+    if not 1 <= byte <= 239:
+        raise ValueError(f'--byte_delay {byte} is outside the 240-byte trace header')
+    raw = np.memmap(segy.path, np.uint8, 'r')
+    start = raw.size - segy.ntraces * segy._dtype.itemsize
+    rows = raw[start:].reshape(segy.ntraces, segy._dtype.itemsize)[:, byte - 1:byte + 1]
+    return np.ascontiguousarray(rows).view('>i2').ravel().astype(np.int64)
+
+
 def scaled_coordinates(scalar, x, y):
     """The header scalar rule of the reference (cube_binning_3D.py:657-668): the sign of the FIRST trace's scalar decides for all;
-    negative: divide by |scalar|, otherwise multiply (a scalar of 0 gives 0, as there)."""
+    negative: divide by |scalar|, otherwise multiply (a scalar of 0 gives 0, as there).  This is binning's rule; `functions.header.scale_coordinates`
+    is the other one of the reference (reprojection's: a scalar of 0 leaves the coordinates as stored, and ``CoordinateUnits`` is honoured)."""
     scalar = np.asarray(scalar, dtype=np.float64)
     x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
     if scalar.size and scalar[0] < 0:
@@ -250,6 +276,30 @@ def update_headers(path, fields):
         mm[name] = values
     mm.flush()
     del mm
+    return path
+
+
+def write_header_words(path, byte, rows, values):
+    """Set the trace-header word at 1-based ``byte`` of traces ``rows`` to ``values``: with the width of the reader's named field that starts
+    there, else as a big-endian int16 (the rule `header_words` reads by)."""
+    segy = SegyFile(path)
+    ntr, size = segy.ntraces, segy._dtype.itemsize
+    name = field_at(byte, missing_ok=True)
+    if name is not None:
+        words = segy.header(name)
+        del segy
+        words[np.asarray(rows)] = values
+        return update_headers(path, {name: words})
+    del segy
+    info = np.iinfo(np.int16)
+    if np.min(values) < info.min or np.max(values) > info.max:
+        raise OverflowError(f'byte {byte}: values outside the range of a 16-bit header word')
+    raw = np.memmap(path, np.uint8, 'r+')
+    start = raw.size - ntr * size
+    packed = np.asarray(values).astype('>i2').reshape(-1, 1).view(np.uint8)
+    raw[start:].reshape(ntr, size)[np.asarray(rows), byte - 1:byte + 1] = packed
+    raw.flush()
+    del raw
     return path
 
 

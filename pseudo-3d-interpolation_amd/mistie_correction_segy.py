@@ -19,13 +19,11 @@ import datetime
 import glob
 import os
 import sys
-from contextlib import redirect_stdout
 from functools import partial
-from shutil import copy2
 
 import numpy as np
 
-from .despiking_2D_segy import clean_log_file, input_files
+from .functions import segy_cli
 from .functions.header import add_processing_info_header, get_textual_header, write_textual_header
 from .functions.mistie import compensate_mistie, compute_misties, find_intersections, line_key, nearest_intersection_vertices
 from .functions.segy import SegyFile, scaled_coordinates, update_samples
@@ -184,27 +182,8 @@ def write_intersections_QC(args, pts_split, line_idx, names, index, dist, xy, sa
 def wrapper_mistie_correction_segy(in_path, offset, offset_ms, args):
     """Shift one SEG-Y file (or its copy) by its line's offset."""
     say = partial(xprint, verbosity=args.verbose)
-    folder, filename = os.path.split(in_path)
-    stem, ext = os.path.splitext(filename)
-    say(f'Processing file < {filename} >', kind='info')
-    out_name = f"{stem}_{'mistie' if args.txt_suffix is None else args.txt_suffix}"
-    out_dir = folder
-    if args.inplace:                                            # supersedes any --output_dir
-        say('Updating SEG-Y inplace', kind='warning')
-        path = in_path
-    else:
-        if args.output_dir is None:
-            say('Creating copy of file in INPUT directory:\n', folder, kind='info')
-        elif os.path.isdir(args.output_dir):
-            say('Creating copy of file in OUTPUT directory:\n', args.output_dir, kind='info')
-            out_dir = args.output_dir
-        else:
-            raise FileNotFoundError(f'The output directory > {args.output_dir} < does not exist')
-        path = os.path.join(out_dir, out_name + ext)
-        if os.path.isfile(path):
-            say('Output file already exists and will be removed!', kind='warning')
-            os.remove(path)
-        copy2(in_path, path)
+    say(f'Processing file < {os.path.basename(in_path)} >', kind='info')
+    path, out_dir, out_name = segy_cli.copied_target(in_path, args, 'mistie', say)
 
     segy = SegyFile(path)
     say(f'n_traces:  {segy.ntraces}', kind='debug')
@@ -229,26 +208,19 @@ def wrapper_mistie_correction_segy(in_path, offset, offset_ms, args):
 
 
 def main(argv=sys.argv):  # noqa
-    stamp = datetime.datetime.now().isoformat(timespec='seconds').replace(':', '')
-    script = os.path.splitext(os.path.basename(__file__))[0]
     args = define_input_args().parse_args(argv[1:])
     say = partial(xprint, verbosity=args.verbose)
     say(args, kind='debug')
 
-    files, folder, single = input_files(args.input_path, args)
+    # not `segy_cli.run`: one file is refused, and the offsets of all lines are solved between listing the files and the logged loop
+    files, folder, single = segy_cli.input_files(args.input_path, args)
     if single:
         raise FileNotFoundError('Invalid input file')          # a directory or a .txt datalist: one line has nothing to tie to
     if not files:
-        sys.exit('No input files to process. Exit process.')
+        sys.exit(segy_cli.MSG_NO_FILES)
     offsets, _ = main_misties(args, files, say)
-
-    log_path = os.path.join(folder, f'{stamp}_{script}.log')
-    with open(log_path, 'w', newline='\n') as log, redirect_stdout(log):
-        say(f'Processing total of < {len(files)} > files', kind='info')
-        for one in files:
-            offset, offset_ms = offsets.get(line_key(one), (0, 0.0))
-            wrapper_mistie_correction_segy(one, offset, offset_ms, args)
-    clean_log_file(log_path)
+    segy_cli.process_list(__file__, folder, files, args,
+                          lambda path: wrapper_mistie_correction_segy(path, *offsets.get(line_key(path), (0, 0.0)), args))
 
 
 if __name__ == '__main__':

@@ -15,18 +15,15 @@ route when that word is 0); the seafloor TWT is computed whenever it is written 
 ``--write_aux`` in mode ``amp`` on unpadded files); mode ``swdep`` on a file with empty water depths is an error with a message.
 """
 import argparse
-import datetime
 import os
 import sys
-from contextlib import redirect_stdout
 from functools import partial
-from shutil import copy2
 
 import numpy as np
 
-from .despiking_2D_segy import clean_log_file, header_words, input_files
+from .functions import segy_cli
 from .functions.header import add_processing_info_header, get_textual_header, write_textual_header
-from .functions.segy import TRACE_FIELDS, SegyFile, update_headers, update_samples
+from .functions.segy import TRACE_FIELDS, SegyFile, header_words, update_headers, update_samples
 from .functions.static import compensate_static, get_static, samples2twt, seafloor_stages, twt2samples
 from .functions.utils import xprint
 
@@ -72,29 +69,6 @@ def define_input_args():  # noqa
 # fmt: on
 
 
-def output_target(in_path, args, say):
-    """(path of the file that is edited, folder of the auxiliary file, output name without extension); the copy is made here."""
-    folder, name = os.path.split(in_path)
-    stem, ext = os.path.splitext(name)
-    out_name = f"{stem}_{'static' if args.txt_suffix is None else args.txt_suffix}"
-    if args.inplace:                                            # supersedes any --output_dir
-        say('Updating SEG-Y inplace', kind='warning')
-        return in_path, folder, out_name
-    if args.output_dir is None:
-        say('Creating copy of file in INPUT directory:\n', folder, kind='info')
-    elif os.path.isdir(args.output_dir):
-        say('Creating copy of file in OUTPUT directory:\n', args.output_dir, kind='info')
-        folder = args.output_dir
-    else:
-        raise FileNotFoundError(f'The output directory > {args.output_dir} < does not exist')
-    target = os.path.join(folder, out_name + ext)
-    if os.path.isfile(target):
-        say('Output file already exists and will be removed!', kind='warning')
-        os.remove(target)
-    copy2(in_path, target)
-    return target, folder, out_name
-
-
 def is_padded(path, hns, nso):
     """A zero-padded file: 'pad' in its path, or an original sample count in the binary header that differs from the sample count."""
     return 'pad' in path or (nso != 0 and nso != hns)
@@ -133,7 +107,7 @@ def wrapper_static_correction_segy(in_path, args):
     """Apply the static correction to one SEG-Y file.  Returns (path, data, data_corrected), both [ns][ntr]."""
     say = partial(xprint, verbosity=args.verbose)
     say(f'Processing file < {os.path.basename(in_path)} >', kind='info')
-    path, aux_dir, out_name = output_target(in_path, args, say)
+    path, aux_dir, out_name = segy_cli.copied_target(in_path, args, 'static', say)
 
     segy = SegyFile(path)
     dt, ns = segy.dt, segy.ns
@@ -181,31 +155,11 @@ def wrapper_static_correction_segy(in_path, args):
 
 
 def main(argv=sys.argv):  # noqa
-    stamp = datetime.datetime.now().isoformat(timespec='seconds').replace(':', '')
-    script = os.path.splitext(os.path.basename(__file__))[0]
     args = define_input_args().parse_args(argv[1:])
     xprint(args, kind='debug', verbosity=args.verbose)
     if args.inplace == (args.output_dir is not None):
         sys.exit(MSG_TARGET)
-
-    files, folder, single = input_files(args.input_path, args)
-    if single:
-        wrapper_static_correction_segy(files[0], args)
-        sys.exit()
-    if not files:
-        sys.exit('No input files to process. Exit process.')
-    log_path = os.path.join(folder, f'{stamp}_{script}.log')
-    failed = 0
-    with open(log_path, 'w', newline='\n') as log, redirect_stdout(log):
-        xprint(f'Processing total of < {len(files)} > files', kind='info', verbosity=args.verbose)
-        for one in files:
-            try:
-                wrapper_static_correction_segy(one, args)
-            except Exception as err:  # noqa: BLE001 -- as the reference: a file that fails is logged, the others are still processed
-                xprint(f'Failed: {err}', kind='error', verbosity=args.verbose)
-                failed += 1
-    clean_log_file(log_path)
-    xprint(f'>{failed}< out of >{len(files)}< files failed!', kind='info', verbosity=args.verbose)
+    segy_cli.run(__file__, args, lambda path: wrapper_static_correction_segy(path, args), catch=True)
 
 
 if __name__ == '__main__':

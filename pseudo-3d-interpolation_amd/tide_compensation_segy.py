@@ -1,7 +1,7 @@
 """
 Step 6 -- compensate the tidal elevation in SEG-Y profile(s) on the GPU, mirror of ``pseudo_3D_interpolation/tide_compensation_segy.py``.
 
-Per file: the header coordinates at ``--src_coords`` are scaled (step 2's ``scale_coordinates``) and brought to geographic degrees
+Per file: the header coordinates at ``--src_coords`` are scaled (``functions/header.scale_coordinates``) and brought to geographic degrees
 (``functions/crs.transform``), the recording time of every trace is read from the header words 157 ... 165, the tide is predicted at every
 position and time from the TPXO9-atlas style model in ``model_dir`` (``functions/tide.tide_predict``: HIP unit ``p3d_tide``), converted to
 samples with 1500 m/s and the file's sample interval, and every trace is shifted by its rounded offset (``functions/tide.compensate_tide``).
@@ -20,22 +20,19 @@ copy is made, so an invalid time (``ValueError`` naming the first such trace) or
 no file behind; ``--write_aux`` with ``--inplace`` writes ``<name>.tid`` beside the file (the reference stops at an undefined name there).
 """
 import argparse
-import datetime
 import os
 import sys
-from contextlib import redirect_stdout
 from functools import partial
-from shutil import copy2
 
 import numpy as np
 
-from .despiking_2D_segy import clean_log_file, input_files
 from .functions import crs as C
-from .functions.header import add_processing_info_header, get_textual_header, write_textual_header
+from .functions import segy_cli
+from .functions.header import (COORDS, MSG_FORCED, TRACE_HEADER_COORDS, add_processing_info_header, get_textual_header, scale_coordinates,
+                               write_textual_header)
 from .functions.segy import SegyFile, update_samples
 from .functions.tide import CONSTITUENTS, DEFAULT_CONSTITUENTS, MSG_MINOR, compensate_tide, header_times, tide_predict
 from .functions.utils import depth2samples, depth2twt, xprint
-from .reproject_segy import COORDS, MSG_FORCED, TRACE_HEADER_COORDS, scale_coordinates
 
 # (names, keywords) per argument, in the reference's order; the help texts are the reference's, so that `--help` reads the same
 ARGUMENTS = [
@@ -65,24 +62,6 @@ def define_input_args():
     return parser
 
 
-def output_target(in_path, args, say):
-    """(path, folder, stem) of the file that is edited and of its ``.tid`` companion; nothing is copied yet."""
-    folder, name = os.path.split(in_path)
-    stem, ext = os.path.splitext(name)
-    if args.inplace:                                            # supersedes any --output_dir
-        say('Updating SEG-Y inplace', kind='warning')
-        return in_path, folder, stem
-    if args.output_dir is None:
-        say('Creating copy of file in INPUT directory:\n', folder, kind='info')
-    elif os.path.isdir(args.output_dir):
-        say('Creating copy of file in OUTPUT directory:\n', args.output_dir, kind='info')
-        folder = args.output_dir
-    else:
-        raise FileNotFoundError(f'The output directory > {args.output_dir} < does not exist')
-    stem = f"{stem}_{'tide' if args.txt_suffix is None else args.txt_suffix}"
-    return os.path.join(folder, stem + ext), folder, stem
-
-
 def aux_lines(tracl, tracr, fldr, times, tides, dt):
     """The lines of the ``.tid`` file (reference columns and formats); ``dt`` in ms."""
     tides_twt = depth2twt(tides)
@@ -98,7 +77,9 @@ def wrapper_tide_compensation(in_path, args):
     if args.correct_minor:
         raise NotImplementedError(MSG_MINOR)
     crs_src = C.parse_crs(args.crs_src)
-    path, folder, stem = output_target(in_path, args, say)
+    path, folder, _ = segy_cli.output_target(in_path, args, 'tide')               # nothing is copied yet
+    segy_cli.say_target(in_path, path, args, say)
+    stem = os.path.splitext(os.path.basename(path))[0]                              # of the file that is edited and of its ``.tid`` companion
 
     segy = SegyFile(in_path)
     dt = segy.dt                                                # sample interval (ms)
@@ -133,11 +114,7 @@ def wrapper_tide_compensation(in_path, args):
     data_comp = compensate_tide(data_src, tides_track, dt, tide_units='meter', units='ms', verbosity=args.verbose)
 
     say('Writing compensated data to disk', kind='debug')
-    if path != in_path:
-        if os.path.isfile(path):
-            say('Output file already exists and will be removed!', kind='warning')
-            os.remove(path)
-        copy2(in_path, path)
+    segy_cli.copy_to_target(in_path, path, say)
     update_samples(path, data_comp.T)
     write_textual_header(path, add_processing_info_header(get_textual_header(path), 'TIDE COMPENSATION', prefix='_TODAY_', newline=True))
 
@@ -151,25 +128,11 @@ def wrapper_tide_compensation(in_path, args):
 
 def main(argv=sys.argv):  # noqa
     """Compensate the tidal effect in SEG-Y file(s)."""
-    stamp = datetime.datetime.now().isoformat(timespec='seconds').replace(':', '')
-    script = os.path.splitext(os.path.basename(__file__))[0]
     args = define_input_args().parse_args(argv[1:])
     if args.verbose is None:                                    # a bare -V (the reference's parser stores None for it)
         args.verbose = 1
     xprint(args, kind='debug', verbosity=args.verbose)
-
-    files, folder, single = input_files(args.input_path, args)
-    if single:
-        wrapper_tide_compensation(files[0], args)
-        sys.exit()
-    if not files:
-        sys.exit('No input files to process. Exit process.')
-    log_path = os.path.join(folder, f'{stamp}_{script}.log')
-    with open(log_path, 'w', newline='\n') as log, redirect_stdout(log):
-        xprint(f'Processing total of < {len(files)} > files', kind='info', verbosity=args.verbose)
-        for one in files:
-            wrapper_tide_compensation(one, args)
-    clean_log_file(log_path)
+    segy_cli.run(__file__, args, lambda path: wrapper_tide_compensation(path, args))
 
 
 if __name__ == '__main__':

@@ -20,6 +20,7 @@ from pseudo_3d_interpolation_amd import delrt_correction_segy as cli3  # noqa: E
 from pseudo_3d_interpolation_amd import delrt_padding_segy as cli4  # noqa: E402
 from pseudo_3d_interpolation_amd.functions import delrt as D  # noqa: E402
 from pseudo_3d_interpolation_amd.functions import segy as S  # noqa: E402
+from pseudo_3d_interpolation_amd.functions import segy_cli  # noqa: E402
 from pseudo_3d_interpolation_amd.functions.header import get_textual_header  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -165,16 +166,16 @@ def test_output_naming_and_skip_of_a_file_with_one_delay(tmp_path, capsys):
     assert cli3.check_varying_DelayRecordingTimes(src) is False and cli3.check_varying_DelayRecordingTimes(src, byte_delay=9) is True
     args4 = cli4.define_input_args().parse_args([src])
     quiet = lambda *a, **k: None  # noqa: E731
-    assert cli4.output_path(src, args4, quiet) == str(tmp_path / 'line_pad.sgy')
+    assert segy_cli.output_target(src, args4, 'pad')[0] == str(tmp_path / 'line_pad.sgy')
     out = tmp_path / 'out'
     out.mkdir()
-    assert cli4.output_path(src, cli4.define_input_args().parse_args([src, '-o', str(out), '--txt_suffix', 'p']), quiet) == str(out / 'line_p.sgy')
+    assert segy_cli.output_target(src, cli4.define_input_args().parse_args([src, '-o', str(out), '--txt_suffix', 'p']), 'pad')[0] == str(out / 'line_p.sgy')
     with pytest.raises(FileNotFoundError):
-        cli4.output_path(src, cli4.define_input_args().parse_args([src, '-o', str(tmp_path / 'missing')]), quiet)
+        segy_cli.output_target(src, cli4.define_input_args().parse_args([src, '-o', str(tmp_path / 'missing')]), 'pad')
     args3 = cli3.define_input_args().parse_args([src, '-o', str(out)])
-    assert cli3.output_target(src, args3, quiet) == str(out / 'line_delrt.sgy') and open(out / 'line_delrt.sgy', 'rb').read() == before
-    assert cli3.output_target(src, cli3.define_input_args().parse_args([src, '-i', '-o', str(out)]), quiet) == src
-    assert cli3.output_target(src, cli3.define_input_args().parse_args([src, '--txt_suffix', 'fix']), quiet) == str(tmp_path / 'line_fix.sgy')
+    assert segy_cli.copied_target(src, args3, 'delrt', quiet)[0] == str(out / 'line_delrt.sgy') and open(out / 'line_delrt.sgy', 'rb').read() == before
+    assert segy_cli.copied_target(src, cli3.define_input_args().parse_args([src, '-i', '-o', str(out)]), 'delrt', quiet)[0] == src
+    assert segy_cli.copied_target(src, cli3.define_input_args().parse_args([src, '--txt_suffix', 'fix']), 'delrt', quiet)[0] == str(tmp_path / 'line_fix.sgy')
     with pytest.raises(FileNotFoundError):
         cli3.main(['x', str(tmp_path / 'missing.sgy')])
 
@@ -239,5 +240,5 @@ def test_correction_at_another_header_byte(monkeypatch, tmp_path):
     seg = S.SegyFile(src)
     want = delrt.copy()
     want[30] = 10
-    assert cli3.header_words(seg, 111).tolist() == want.tolist() and set(seg.header('DelayRecordingTime').tolist()) == {0}
+    assert S.header_words(seg, 111).tolist() == want.tolist() and set(seg.header('DelayRecordingTime').tolist()) == {0}
     assert seg.traces().tobytes() == np.ascontiguousarray(data.T).tobytes()

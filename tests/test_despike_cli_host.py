@@ -9,7 +9,7 @@ import pytest
 
 from conftest import ROOT
 from pseudo_3d_interpolation_amd import despiking_2D_segy as cli
-from pseudo_3d_interpolation_amd.functions import header, segy
+from pseudo_3d_interpolation_amd.functions import header, segy, segy_cli
 
 # (dest, default, choices) of the reference's parser (despiking_2D_segy.py, define_input_args)
 RECORDED = [('input_path', None, None), ('output_dir', None, None), ('inplace', False, None), ('suffix', 'sgy', None), ('filename_suffix', None, None),
@@ -29,11 +29,11 @@ def test_parser_equals_the_recorded_list():
 
 def test_output_naming(tmp_path):
     ns = types.SimpleNamespace
-    assert cli.output_path('/d/line1.sgy', ns(inplace=False, output_dir=None, txt_suffix='despk')) == '/d/line1_despk.sgy'
-    assert cli.output_path('/d/line1.segy', ns(inplace=False, output_dir=str(tmp_path), txt_suffix='x')) == str(tmp_path / 'line1_x.segy')
-    assert cli.output_path('/d/line1.sgy', ns(inplace=True, output_dir=str(tmp_path), txt_suffix='x')) == '/d/line1.sgy'
+    assert segy_cli.output_target('/d/line1.sgy', ns(inplace=False, output_dir=None, txt_suffix='despk'), 'despk')[0] == '/d/line1_despk.sgy'
+    assert segy_cli.output_target('/d/line1.segy', ns(inplace=False, output_dir=str(tmp_path), txt_suffix='x'), 'despk')[0] == str(tmp_path / 'line1_x.segy')
+    assert segy_cli.output_target('/d/line1.sgy', ns(inplace=True, output_dir=str(tmp_path), txt_suffix='x'), 'despk')[0] == '/d/line1.sgy'
     with pytest.raises(FileNotFoundError, match='does not exist'):
-        cli.output_path('/d/line1.sgy', ns(inplace=False, output_dir=str(tmp_path / 'nope'), txt_suffix='x'))
+        segy_cli.output_target('/d/line1.sgy', ns(inplace=False, output_dir=str(tmp_path / 'nope'), txt_suffix='x'), 'despk')
 
 
 @pytest.mark.parametrize('extra,msg', [(['-wo', '100', '-t', '2'], 'window overlap'), (['-t', '0'], 'Threshold factor'), ([], 'Threshold factor')])
@@ -100,8 +100,8 @@ def test_in_place_sample_update_round_trip(tmp_path, fmt):
         assert f.traces().tobytes() == y.tobytes()
     else:
         assert np.abs(f.traces() - y).max() <= 2.0**-20 * np.abs(y).max()     # IBM mantissa: 24 bits with up to 3 leading zeros
-    assert f.header('SourceX').tolist() == list(range(0, 90, 10)) and cli.header_words(f, 109).tolist() == (np.arange(9) // 4).tolist()
-    assert cli.header_words(f, 71).tolist() == [0] * 9 and cli.header_words(f, 111).tolist() == [0] * 9
+    assert f.header('SourceX').tolist() == list(range(0, 90, 10)) and segy.header_words(f, 109).tolist() == (np.arange(9) // 4).tolist()
+    assert segy.header_words(f, 71).tolist() == [0] * 9 and segy.header_words(f, 111).tolist() == [0] * 9
     after = open(p, 'rb').read()
     size = 240 + 41 * 4
     assert after[:3600] == before[:3600] and all(after[3600 + k * size:3840 + k * size] == before[3600 + k * size:3840 + k * size] for k in range(9))

@@ -22,7 +22,7 @@ from pseudo_3d_interpolation_amd import reproject_segy as cli  # noqa: E402
 from pseudo_3d_interpolation_amd.functions import crs as C  # noqa: E402
 from pseudo_3d_interpolation_amd.functions import filter as F  # noqa: E402
 from pseudo_3d_interpolation_amd.functions import segy as S  # noqa: E402
-from pseudo_3d_interpolation_amd.functions.header import get_textual_header  # noqa: E402
+from pseudo_3d_interpolation_amd.functions.header import get_textual_header, unscale_coordinates  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = np.load(os.path.join(ROOT, 'tests', 'golden', 'reproject.npz'))
@@ -74,7 +74,7 @@ def test_header_fixture_is_consistent():
     E, N = H.tm_forward(lon, lat, G['proj/utm60s_wgs84/prm'])
     assert lon.size == 300 and np.abs(E - G['hdr/E']).max() <= TOL_M and np.abs(N - G['hdr/N']).max() <= TOL_M
     for sc in G['hdr/scalars'].tolist():
-        x, y = cli.unscale_coordinates(E, N, sc)
+        x, y = unscale_coordinates(E, N, sc)
         assert np.array_equal(x, G[f'hdr/{sc}/x']) and np.array_equal(y, G[f'hdr/{sc}/y']), sc
         assert np.abs(G[f'hdr/{sc}/y']).max() < 2**31
 
@@ -253,7 +253,7 @@ def test_utm32_to_utm33(on_host, tmp_path):
     with pytest.raises(SystemExit):
         cli.main(['x', src, '--crs_src', 'EPSG:32632', '--crs_dst', 'EPSG:32633', '-sc', '-10', '--txt_suffix', 'z33'])
     out = S.SegyFile(str(tmp_path / 'line_z33.sgy'))
-    wx, wy = cli.unscale_coordinates(*host_grid_to_grid(C.parse_crs(32632), C.parse_crs(32633), x_in / 100, y_in / 100), -10)
+    wx, wy = unscale_coordinates(*host_grid_to_grid(C.parse_crs(32632), C.parse_crs(32633), x_in / 100, y_in / 100), -10)
     assert np.array_equal(out.header('SourceX'), wx) and np.array_equal(out.header('SourceY'), wy)
     # the input was rounded to centimetres (0.005 m, stretched by at most a few 1e-4 between the grids), the output to decimetres (0.05 m)
     assert np.abs(out.header('SourceX') / 10 - G['z2z/E_dst']).max() <= 0.056 and np.abs(out.header('SourceY') / 10 - G['z2z/N_dst']).max() <= 0.056
