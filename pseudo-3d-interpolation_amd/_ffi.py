@@ -318,33 +318,47 @@ class DeviceBuffer:
             self.ptr = None
 
 
-class WaveletPlan64:
-    """p3d_wplan64 wrapper: the WAVELET POCS loop in double precision (include/p3d.h) for complex128 / float64 cubes, and for complex64 /
-    float32 cubes on request (``precision='reference'``)."""
-    _DT = {np.dtype(np.complex128): P3D_C128, np.dtype(np.float64): P3D_F64, np.dtype(np.complex64): P3D_C64, np.dtype(np.float32): P3D_F32}
+def _tau_table(tau, shape):
+    """Thresholds broadcast to ``shape`` -> float64 ``shape + (2,)`` of (Re, Im) pairs: the layout every C entry takes."""
+    tau = np.broadcast_to(np.asarray(tau), shape)
+    t = np.empty(tau.shape + (2,), np.float64)
+    t[..., 0] = tau.real
+    t[..., 1] = tau.imag if np.iscomplexobj(tau) else 0.0
+    return t
 
-    def __init__(self, nil, nxl, max_slices, wavelet="coif5", level=None, device=0):
-        self.nil, self.nxl, self.max_slices, self.device = int(nil), int(nxl), int(max_slices), int(device)
-        self.wavelet = wavelet
-        bank = wavelet if isinstance(wavelet, (tuple, list)) else wavelet_filters(wavelet)
-        bank = [np.ascontiguousarray(b, dtype=np.float64) for b in bank]
-        if len(bank) != 4 or len({b.size for b in bank}) != 1:
-            raise ValueError("a filter bank is (dec_lo, dec_hi, rec_lo, rec_hi) of equal length")
-        h = C.c_void_p()
-        check(lib().p3d_wavelet64_plan_create(C.byref(h), self.device, self.nil, self.nxl, self.max_slices, *map(_ptr, bank),
-                                              bank[0].size, -1 if level is None else int(level)))
-        self.handle = h
-        nlev, ncoef = C.c_int(0), C.c_int64(0)
-        check(lib().p3d_wavelet64_info(self.handle, C.byref(nlev), C.byref(ncoef)))
-        self.nlev, self.ncoef = nlev.value, ncoef.value
+
+def _filter_bank(wavelet):
+    """A wavelet name or (dec_lo, dec_hi, rec_lo, rec_hi) -> the four float64 filters of equal length."""
+    bank = wavelet if isinstance(wavelet, (tuple, list)) else wavelet_filters(wavelet)
+    bank = [np.ascontiguousarray(b, dtype=np.float64) for b in bank]
+    if len(bank) != 4 or len({b.size for b in bank}) != 1:
+        raise ValueError("a filter bank is (dec_lo, dec_hi, rec_lo, rec_hi) of equal length")
+    return bank
+
+
+def _real_psi(psi):
+    """Shearlet spectra (nil, nxl, nsh), real."""
+    psi = np.asarray(psi)
+    if psi.ndim != 3:
+        raise ValueError(f"Psi must be (nil, nxl, nshearlets), got shape {psi.shape}")
+    if np.iscomplexobj(psi):
+        raise NotImplementedError("complex shearlet spectra (realCoefficients=False) are not implemented")
+    return psi
+
+
+class _PlanBase:
+    """What the six plan classes share: the life of the C handle (``_DESTROY``) and the marshalling of one POCS job for the entry ``_RUN``
+    (thresholds per slice and iteration: ``_tau_shape()``).  This one holds the float32 side: complex64 / float32 cubes, a float32 mask."""
+    _DESTROY = _RUN = None
+    _MASK_DT = np.float32
 
     def close(self):
         if getattr(self, "handle", None):
-            lib().p3d_wavelet64_plan_destroy(self.handle)
+            getattr(lib(), self._DESTROY)(self.handle)
             self.handle = None
 
     def __del__(self):
-        if lib is not None:
+        if lib is not None:   # (module globals are gone while the interpreter shuts down: the process's device memory goes with it)
             self.close()
 
     def __enter__(self):
@@ -357,52 +371,101 @@ class WaveletPlan64:
         x = np.asarray(x)
         if x.ndim == 2:
             x = x[None]
+        if x.ndim != 3 or x.shape[1:] != (self.nil, self.nxl):
+            raise ValueError(f"expected (nslices, {self.nil}, {self.nxl}), got {x.shape}")
+        if x.shape[0] > self.max_slices:
+            raise ValueError(f"{x.shape[0]} slices > max_slices {self.max_slices}")
+        if np.iscomplexobj(x):
+            return np.ascontiguousarray(x, dtype=np.complex64), P3D_C64
+        return np.ascontiguousarray(x, dtype=np.float32), P3D_F32
+
+    def _tau_shape(self):
+        return ()
+
+    def _host_job(self, x, mask):
+        """The host cube as the library takes it, its dtype code, the mask in the plan's precision and an empty result."""
+        xc, dt = self._cube(x)
+        m = np.ascontiguousarray(mask, dtype=self._MASK_DT)
+        if m.shape != (self.nil, self.nxl):
+            raise ValueError(f"mask shape {m.shape} != {(self.nil, self.nxl)}")
+        return xc, dt, m, np.empty_like(xc)
+
+    def _run_entry(self, entry, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op, version, eps, alpha, active, profile=False, want_sums=True,
+                   primed=False):
+        """One call of a p3d_*_run entry on raw pointers.  Returns (niter_done, sums or None, device ms of the loop)."""
+        t = _tau_table(tau, (n, niter) + self._tau_shape())
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+        prm = Plan._params(niter, thresh_op, version, eps, alpha, profile, primed)
+        done = np.zeros(n, np.int32)
+        sums = np.zeros((niter + 1, n), np.float64) if want_sums else None
+        ms = C.c_double(0.0)
+        check(getattr(lib(), entry)(self.handle, x_ptr, dtype, mask_ptr, _ptr(t), None if act is None else _ptr(act), C.byref(prm), out_ptr, n,
+                                    _ptr(done), None if sums is None else _ptr(sums), C.byref(ms)))
+        return done, sums, ms.value
+
+    def stats(self, x):
+        """`stats_dev` of a host cube."""
+        xc, dt = self._cube(x)
+        return self.stats_dev(xc.ctypes.data, dt, xc.shape[0])
+
+    def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
+        """Host arrays in, host array out (as `_cube` converts ``x``).  tau: anything that broadcasts to (nslices, niter) + the plan's thresholds per
+        iteration, real or complex.  Returns (out, niter_done, sums, elapsed_ms)."""
+        xc, dt, m, out = self._host_job(x, mask)
+        done, sums, ms = self.run_dev(xc.ctypes.data, dt, m.ctypes.data, tau, niter, out.ctypes.data, xc.shape[0], thresh_op=thresh_op, version=version,
+                                      eps=eps, alpha=alpha, active=active)
+        return out, done, sums, ms
+
+    def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
+        """`run` on raw pointers (host or device; the mask in the plan's precision, [nil][nxl]).  Returns (niter_done, sums, device ms of the loop)."""
+        return self._run_entry(self._RUN, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op, version, eps, alpha, active)
+
+
+class _PlanBase64(_PlanBase):
+    """... and the double-precision side: cubes of all four types as they are, a float64 mask."""
+    _DT = {np.dtype(np.complex128): P3D_C128, np.dtype(np.float64): P3D_F64, np.dtype(np.complex64): P3D_C64, np.dtype(np.float32): P3D_F32}
+    _MASK_DT = np.float64
+
+    def _cube(self, x):
+        x = np.asarray(x)
+        if x.ndim == 2:
+            x = x[None]
         if x.ndim != 3 or x.shape[1:] != (self.nil, self.nxl) or x.shape[0] > self.max_slices:
             raise ValueError(f"expected (<= {self.max_slices}, {self.nil}, {self.nxl}), got {x.shape}")
         if x.dtype not in self._DT:
             x = x.astype(np.complex128 if np.iscomplexobj(x) else np.float64)
         return np.ascontiguousarray(x), self._DT[x.dtype]
 
+
+class WaveletPlan64(_PlanBase64):
+    """p3d_wplan64 wrapper: the WAVELET POCS loop in double precision (include/p3d.h) for complex128 / float64 cubes, and for complex64 /
+    float32 cubes on request (``precision='reference'``).  tau: (nslices, niter, nlev, 3), levels coarse -> fine."""
+    _DESTROY, _RUN = "p3d_wavelet64_plan_destroy", "p3d_wavelet64_run"
+
+    def __init__(self, nil, nxl, max_slices, wavelet="coif5", level=None, device=0):
+        self.nil, self.nxl, self.max_slices, self.device = int(nil), int(nxl), int(max_slices), int(device)
+        self.wavelet = wavelet
+        bank = _filter_bank(wavelet)
+        h = C.c_void_p()
+        check(lib().p3d_wavelet64_plan_create(C.byref(h), self.device, self.nil, self.nxl, self.max_slices, *map(_ptr, bank),
+                                              bank[0].size, -1 if level is None else int(level)))
+        self.handle = h
+        nlev, ncoef = C.c_int(0), C.c_int64(0)
+        check(lib().p3d_wavelet64_info(self.handle, C.byref(nlev), C.byref(ncoef)))
+        self.nlev, self.ncoef = nlev.value, ncoef.value
+
+    def _tau_shape(self):
+        return (self.nlev, 3)
+
     @staticmethod
     def _tau(tau, n, niter, nlev):
-        tau = np.broadcast_to(np.asarray(tau), (n, niter, nlev, 3))
-        t = np.empty(tau.shape + (2,), np.float64)
-        t[..., 0] = tau.real
-        t[..., 1] = tau.imag if np.iscomplexobj(tau) else 0.0
-        return t
-
-    def stats(self, x):
-        """(nslices, nlev, 3, 4): Re / Im of the lexicographic max, max |d|, min |d| per detail array (coarsest level first), in double."""
-        xc, dt = self._cube(x)
-        return self.stats_dev(xc.ctypes.data, dt, xc.shape[0])
+        return _tau_table(tau, (n, niter, nlev, 3))
 
     def stats_dev(self, x_ptr, dtype, n):
+        """(nslices, nlev, 3, 4): Re / Im of the lexicographic max, max |d|, min |d| per detail array (coarsest level first), in double."""
         st = np.empty((n, self.nlev, 3, 4), np.float64)
-        check(lib().p3d_wavelet64_stats(self.handle, C.c_void_p(x_ptr), dtype, n, _ptr(st)))
+        check(lib().p3d_wavelet64_stats(self.handle, x_ptr, dtype, n, _ptr(st)))
         return st
-
-    def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
-        """Host arrays in, host array out (dtype of ``x``).  tau: (nslices, niter, nlev, 3) real or complex.  Returns (out, niter_done, sums, ms)."""
-        xc, dt = self._cube(x)
-        m = np.ascontiguousarray(mask, dtype=np.float64)
-        if m.shape != (self.nil, self.nxl):
-            raise ValueError(f"mask shape {m.shape} != {(self.nil, self.nxl)}")
-        out = np.empty_like(xc)
-        done, sums, ms = self.run_dev(xc.ctypes.data, dt, m.ctypes.data, tau, niter, out.ctypes.data, xc.shape[0], thresh_op=thresh_op, version=version,
-                                      eps=eps, alpha=alpha, active=active)
-        return out, done, sums, ms
-
-    def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
-        """`run` on raw pointers (host or device; the mask is DOUBLE [nil][nxl]).  Returns (niter_done, sums, device ms of the loop)."""
-        t = self._tau(tau, n, niter, self.nlev)
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
-        done = np.zeros(n, np.int32)
-        sums = np.zeros((niter + 1, n), np.float64)
-        ms = C.c_double(0.0)
-        check(lib().p3d_wavelet64_run(self.handle, C.c_void_p(x_ptr), dtype, C.c_void_p(mask_ptr), _ptr(t), None if act is None else _ptr(act),
-                                      C.byref(prm), C.c_void_p(out_ptr), n, _ptr(done), _ptr(sums), C.byref(ms)))
-        return done, sums, ms.value
 
 
 class DeviceArray:
@@ -517,8 +580,9 @@ class PinnedBuffer:
             self.ptr = None
 
 
-class Plan:
+class Plan(_PlanBase):
     """p3d_plan wrapper: one device, one (nil, nxl) slice shape, up to ``max_slices`` per call."""
+    _DESTROY = "p3d_plan_destroy"
 
     def __init__(self, nil, nxl, max_slices, device=0):
         self.nil, self.nxl, self.max_slices, self.device = int(nil), int(nxl), int(max_slices), int(device)
@@ -526,34 +590,7 @@ class Plan:
         check(lib().p3d_plan_create(C.byref(h), self.device, self.nil, self.nxl, self.max_slices))
         self.handle = h
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().p3d_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        if lib is not None:   # (module globals are gone while the interpreter shuts down: the process's device memory goes with it)
-            self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     # ---- helpers ---------------------------------------------------------------------------
-    def _cube(self, x):
-        x = np.asarray(x)
-        if x.ndim == 2:
-            x = x[None]
-        if x.ndim != 3 or x.shape[1:] != (self.nil, self.nxl):
-            raise ValueError(f"expected (nslices, {self.nil}, {self.nxl}), got {x.shape}")
-        if x.shape[0] > self.max_slices:
-            raise ValueError(f"{x.shape[0]} slices > max_slices {self.max_slices}")
-        if np.iscomplexobj(x):
-            return np.ascontiguousarray(x, dtype=np.complex64), P3D_C64
-        return np.ascontiguousarray(x, dtype=np.float32), P3D_F32
-
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)
 
@@ -576,9 +613,7 @@ class Plan:
         squeeze = x.ndim == 2
         xc, _ = self._cube(x.astype(np.complex64, copy=False))
         n = xc.shape[0]
-        t = np.empty((n, 2), np.float64)
-        tau = np.broadcast_to(np.asarray(tau, dtype=np.complex128), (n,))
-        t[:, 0], t[:, 1] = tau.real, tau.imag
+        t = _tau_table(tau, (n,))
         out = np.empty_like(xc)
         check(lib().p3d_fft2_shrink_c64(self.handle, _ptr(xc), _ptr(t), P3D_OP[thresh_op], _ptr(out), n))
         return out[0] if squeeze else out
@@ -633,30 +668,15 @@ class Plan:
 
     @staticmethod
     def _tau(tau, nslices, niter):
-        tau = np.asarray(tau)
-        t = np.empty((nslices, niter, 2), np.float64)
-        t[..., 0] = np.broadcast_to(tau.real, (nslices, niter))
-        t[..., 1] = np.broadcast_to(tau.imag, (nslices, niter)) if np.iscomplexobj(tau) else 0.0
-        return t
+        return _tau_table(tau, (nslices, niter))
 
     def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None,
             profile=False):
         """Host arrays in, host arrays out.  Returns (out, niter_done, sums, elapsed_ms)."""
-        xc, dt = self._cube(x)
-        n = xc.shape[0]
-        m = np.ascontiguousarray(mask, dtype=np.float32)
-        if m.shape != (self.nil, self.nxl):
-            raise ValueError(f"mask shape {m.shape} != {(self.nil, self.nxl)}")
-        t = self._tau(tau, n, niter)
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = self._params(niter, thresh_op, version, eps, alpha, profile)
-        out = np.empty_like(xc)
-        done = np.zeros(n, np.int32)
-        sums = np.zeros((niter + 1, n), np.float64)
-        ms = C.c_double(0.0)
-        check(lib().p3d_pocs_run(self.handle, _ptr(xc), dt, _ptr(m), _ptr(t), None if act is None else _ptr(act),
-                                 C.byref(prm), _ptr(out), n, _ptr(done), _ptr(sums), C.byref(ms)))
-        return out, done, sums, ms.value
+        xc, dt, m, out = self._host_job(x, mask)
+        done, sums, ms = self._run_entry("p3d_pocs_run", _ptr(xc), dt, _ptr(m), tau, niter, _ptr(out), xc.shape[0], thresh_op, version, eps, alpha,
+                                         active, profile)
+        return out, done, sums, ms
 
     def prime_dev(self, x_ptr, dtype, mask_ptr, nslices):
         """`stats_dev` that doubles as the first pass of the job: follow it with ``run_dev(..., primed=True)`` on the same
@@ -672,17 +692,9 @@ class Plan:
 
     def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, nslices, thresh_op="hard", version="regular",
                 eps=0.0, alpha=1.0, active=None, profile=False, want_sums=True, primed=False):
-        """Device pointers in/out (cube stays resident in HBM).  Returns (niter_done, sums, elapsed_ms)."""
-        t = self._tau(tau, nslices, niter)
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = self._params(niter, thresh_op, version, eps, alpha, profile, primed)
-        done = np.zeros(nslices, np.int32)
-        sums = np.zeros((niter + 1, nslices), np.float64) if want_sums else None
-        ms = C.c_double(0.0)
-        check(lib().p3d_pocs_run_dev(self.handle, x_ptr, dtype, mask_ptr, _ptr(t), None if act is None else _ptr(act),
-                                     C.byref(prm), out_ptr, nslices, _ptr(done), None if sums is None else _ptr(sums),
-                                     C.byref(ms)))
-        return done, sums, ms.value
+        """Device pointers in/out (cube stays resident in HBM).  Returns (niter_done, sums -- None unless ``want_sums`` --, elapsed_ms)."""
+        return self._run_entry("p3d_pocs_run_dev", x_ptr, dtype, mask_ptr, tau, niter, out_ptr, nslices, thresh_op, version, eps, alpha, active, profile,
+                               want_sums, primed)
 
     def last_sparsity(self):
         """Fraction of 8-column spectrum blocks that kept a coefficient in the last run (-1: dense path)."""
@@ -696,8 +708,6 @@ class Plan:
         return {"colpass_ms": cm.value, "colpass_launches": cn.value, "rowpass_ms": rm.value,
                 "rowpass_launches": rn.value}
 
-
-# ---- steps 12 / 14: time <-> frequency along the slice axis ------------------------------------------------
 
 # ---- WAVELET variant -----------------------------------------------------------------------
 _BANKS = None
@@ -717,16 +727,15 @@ def wavelet_filters(name):
     return tuple(np.ascontiguousarray(b[k], dtype=np.float64) for k in ("dec_lo", "dec_hi", "rec_lo", "rec_hi"))
 
 
-class WaveletPlan:
-    """p3d_wplan wrapper: multilevel 2-D DWT ('smooth' extension) of (nil, nxl) slices and the WAVELET POCS loop."""
+class WaveletPlan(_PlanBase):
+    """p3d_wplan wrapper: multilevel 2-D DWT ('smooth' extension) of (nil, nxl) slices and the WAVELET POCS loop.  tau: (nslices, niter, nlev, 3),
+    levels coarse -> fine."""
+    _DESTROY, _RUN = "p3d_wavelet_plan_destroy", "p3d_wavelet_run"
 
     def __init__(self, nil, nxl, max_slices, wavelet="coif5", level=None, device=0):
         self.nil, self.nxl, self.max_slices, self.device = int(nil), int(nxl), int(max_slices), int(device)
         self.wavelet = wavelet
-        bank = wavelet if isinstance(wavelet, (tuple, list)) else wavelet_filters(wavelet)
-        bank = [np.ascontiguousarray(b, dtype=np.float64) for b in bank]
-        if len(bank) != 4 or len({b.size for b in bank}) != 1:
-            raise ValueError("a filter bank is (dec_lo, dec_hi, rec_lo, rec_hi) of equal length")
+        bank = _filter_bank(wavelet)
         h = C.c_void_p()
         check(lib().p3d_wavelet_plan_create(C.byref(h), self.device, self.nil, self.nxl, self.max_slices, *map(_ptr, bank),
                                             bank[0].size, -1 if level is None else int(level)))
@@ -738,22 +747,8 @@ class WaveletPlan:
         check(lib().p3d_wavelet_info(self.handle, None, None, _ptr(shapes)))
         self.shapes = [tuple(int(v) for v in r) for r in shapes]   # cA, then details coarsest -> finest
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().p3d_wavelet_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        if lib is not None:   # (module globals are gone while the interpreter shuts down: the process's device memory goes with it)
-            self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    _cube = Plan._cube
+    def _tau_shape(self):
+        return (self.nlev, 3)
 
     def unpack(self, vec):
         """flat coefficient vector of ONE slice -> [cA, (cH, cV, cD), ...] like pywt.wavedec2."""
@@ -788,94 +783,25 @@ class WaveletPlan:
         check(lib().p3d_waverec2_c64(self.handle, _ptr(coef), _ptr(out), coef.shape[0]))
         return out[0] if squeeze else out
 
-    def stats(self, x):
-        """(nslices, nlev, 3, 4): Re/Im of the lexicographic max, max |d|, min |d| per detail array (coarsest level first)."""
-        xc, dt = self._cube(x)
-        st = np.empty((xc.shape[0], self.nlev, 3, 4), np.float64)
-        check(lib().p3d_wavelet_stats(self.handle, _ptr(xc), dt, xc.shape[0], _ptr(st)))
-        return st
-
-    def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
-        """tau: (nslices, niter, nlev, 3) real or complex.  Returns (out, niter_done, sums, elapsed_ms)."""
-        xc, dt = self._cube(x)
-        n = xc.shape[0]
-        m = np.ascontiguousarray(mask, dtype=np.float32)
-        if m.shape != (self.nil, self.nxl):
-            raise ValueError(f"mask shape {m.shape} != {(self.nil, self.nxl)}")
-        tau = np.broadcast_to(np.asarray(tau), (n, niter, self.nlev, 3))
-        t = np.empty(tau.shape + (2,), np.float64)
-        t[..., 0] = tau.real
-        t[..., 1] = tau.imag if np.iscomplexobj(tau) else 0.0
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
-        out = np.empty_like(xc)
-        done = np.zeros(n, np.int32)
-        sums = np.zeros((niter + 1, n), np.float64)
-        ms = C.c_double(0.0)
-        check(lib().p3d_wavelet_run(self.handle, _ptr(xc), dt, _ptr(m), _ptr(t), None if act is None else _ptr(act),
-                                    C.byref(prm), _ptr(out), n, _ptr(done), _ptr(sums), C.byref(ms)))
-        return out, done, sums, ms.value
-
     def stats_dev(self, x_ptr, dtype, n):
-        """`stats` for a cube resident on the device (raw pointer, P3D_C64 / P3D_F32)."""
+        """(nslices, nlev, 3, 4): Re/Im of the lexicographic max, max |d|, min |d| per detail array (coarsest level first); raw pointer (host or
+        device), P3D_C64 / P3D_F32."""
         st = np.empty((n, self.nlev, 3, 4), np.float64)
-        check(lib().p3d_wavelet_stats(self.handle, C.c_void_p(x_ptr), dtype, n, _ptr(st)))
+        check(lib().p3d_wavelet_stats(self.handle, x_ptr, dtype, n, _ptr(st)))
         return st
-
-    def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op="hard", version="regular", eps=0.0, alpha=1.0,
-                active=None):
-        """`run` on device-resident buffers (raw pointers; the library accepts host or device pointers for the cubes).  Returns
-        (niter_done, sums, device ms of the loop)."""
-        tau = np.broadcast_to(np.asarray(tau), (n, niter, self.nlev, 3))
-        t = np.empty(tau.shape + (2,), np.float64)
-        t[..., 0] = tau.real
-        t[..., 1] = tau.imag if np.iscomplexobj(tau) else 0.0
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
-        done = np.zeros(n, np.int32)
-        sums = np.zeros((niter + 1, n), np.float64)
-        ms = C.c_double(0.0)
-        check(lib().p3d_wavelet_run(self.handle, C.c_void_p(x_ptr), dtype, C.c_void_p(mask_ptr), _ptr(t), None if act is None else _ptr(act),
-                                    C.byref(prm), C.c_void_p(out_ptr), n, _ptr(done), _ptr(sums), C.byref(ms)))
-        return done, sums, ms.value
 
 
 # ---- the loop in the reference's precision ---------------------------------------------------
-class Plan64:
+class Plan64(_PlanBase64):
     """p3d_plan64 wrapper: the FFT POCS loop in double precision (include/p3d.h) for complex128 / float64 cubes, and for complex64 /
     float32 cubes whose reference run is a double-precision one (soft / garrote / FPOCS / APOCS, or any run under NumPy < 2)."""
-    _DT = {np.dtype(np.complex128): P3D_C128, np.dtype(np.float64): P3D_F64, np.dtype(np.complex64): P3D_C64, np.dtype(np.float32): P3D_F32}
+    _DESTROY, _RUN = "p3d_plan64_destroy", "p3d_pocs64_run"
 
     def __init__(self, nil, nxl, max_slices, device=0):
         self.nil, self.nxl, self.max_slices, self.device = int(nil), int(nxl), int(max_slices), int(device)
         h = C.c_void_p()
         check(lib().p3d_plan64_create(C.byref(h), self.device, self.nil, self.nxl, self.max_slices))
         self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().p3d_plan64_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        if lib is not None:
-            self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _cube(self, x):
-        x = np.asarray(x)
-        if x.ndim == 2:
-            x = x[None]
-        if x.ndim != 3 or x.shape[1:] != (self.nil, self.nxl) or x.shape[0] > self.max_slices:
-            raise ValueError(f"expected (<= {self.max_slices}, {self.nil}, {self.nxl}), got {x.shape}")
-        if x.dtype not in self._DT:
-            x = x.astype(np.complex128 if np.iscomplexobj(x) else np.float64)
-        return np.ascontiguousarray(x), self._DT[x.dtype]
 
     def fft2(self, x, inverse=False):
         """Test hook: fft2 / ifft2 of complex128 slices through the loop's own passes (``p3d_fft2_c128``)."""
@@ -889,61 +815,21 @@ class Plan64:
         check(lib().p3d_fft2_c128(self.handle, _ptr(xc), _ptr(out), xc.shape[0], 1 if inverse else 0))
         return out[0] if squeeze else out
 
-    def stats(self, x):
-        """(nslices, 6) float64, the layout of ``Plan.stats``: statistics of the double-precision ``fft2(x)``."""
-        xc, dt = self._cube(x)
-        st = np.empty((xc.shape[0], 6), np.float64)
-        check(lib().p3d_pocs64_stats(self.handle, _ptr(xc), dt, xc.shape[0], _ptr(st)))
-        return st
-
-    def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
-        """Host arrays in, host arrays out (dtype of ``x``).  Returns (out, niter_done, sums, elapsed_ms)."""
-        xc, dt = self._cube(x)
-        n = xc.shape[0]
-        m = np.ascontiguousarray(mask, dtype=np.float64)
-        if m.shape != (self.nil, self.nxl):
-            raise ValueError(f"mask shape {m.shape} != {(self.nil, self.nxl)}")
-        t = Plan._tau(tau, n, niter)
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
-        out = np.empty_like(xc)
-        done = np.zeros(n, np.int32)
-        sums = np.zeros((niter + 1, n), np.float64)
-        ms = C.c_double(0.0)
-        check(lib().p3d_pocs64_run(self.handle, _ptr(xc), dt, _ptr(m), _ptr(t), None if act is None else _ptr(act), C.byref(prm), _ptr(out), n,
-                                   _ptr(done), _ptr(sums), C.byref(ms)))
-        return out, done, sums, ms.value
-
     def stats_dev(self, x_ptr, dtype, n):
-        """`stats` for a cube resident on the device (raw pointer; dtype P3D_C128 / P3D_F64 / P3D_C64 / P3D_F32)."""
+        """(nslices, 6) float64, the layout of ``Plan.stats``: statistics of the double-precision ``fft2(x)``; raw pointer (host or device)."""
         st = np.empty((n, 6), np.float64)
-        check(lib().p3d_pocs64_stats(self.handle, C.c_void_p(x_ptr), dtype, n, _ptr(st)))
+        check(lib().p3d_pocs64_stats(self.handle, x_ptr, dtype, n, _ptr(st)))
         return st
-
-    def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
-        """`run` on device-resident buffers (raw pointers; the mask is DOUBLE [nil][nxl]).  Returns (niter_done, sums, device ms of the loop)."""
-        t = Plan._tau(tau, n, niter)
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
-        done = np.zeros(n, np.int32)
-        sums = np.zeros((niter + 1, n), np.float64)
-        ms = C.c_double(0.0)
-        check(lib().p3d_pocs64_run(self.handle, C.c_void_p(x_ptr), dtype, C.c_void_p(mask_ptr), _ptr(t), None if act is None else _ptr(act), C.byref(prm),
-                                   C.c_void_p(out_ptr), n, _ptr(done), _ptr(sums), C.byref(ms)))
-        return done, sums, ms.value
 
 
 # ---- SHEARLET variant ----------------------------------------------------------------------
-class ShearletPlan:
+class ShearletPlan(_PlanBase):
     """p3d_splan wrapper: frequency-domain shearlet frame with caller-supplied spectra ``psi`` (nil, nxl, nsh) -- the layout of
-    ``FFST.scalesShearsAndSpectra`` -- and the SHEARLET POCS loop for up to ``max_slices`` slices per call."""
+    ``FFST.scalesShearsAndSpectra`` -- and the SHEARLET POCS loop for up to ``max_slices`` slices per call.  tau: (nslices, niter, nsh)."""
+    _DESTROY, _RUN = "p3d_shearlet_plan_destroy", "p3d_shearlet_run"
 
     def __init__(self, psi, max_slices=1, device=0):
-        psi = np.asarray(psi)
-        if psi.ndim != 3:
-            raise ValueError(f"Psi must be (nil, nxl, nshearlets), got shape {psi.shape}")
-        if np.iscomplexobj(psi):
-            raise NotImplementedError("complex shearlet spectra (realCoefficients=False) are not implemented")
+        psi = _real_psi(psi)
         self.nil, self.nxl, self.nsh = (int(v) for v in psi.shape)
         self.max_slices, self.device = int(max_slices), int(device)
         dev_psi = np.ascontiguousarray(np.moveaxis(psi, -1, 0), dtype=np.float32)
@@ -956,22 +842,8 @@ class ShearletPlan:
         # float32 cubes on symmetric spectra additionally work on Hermitian half slices, two columns per transform
         self.row_group_fraction, self.paired = frac.value, bool(paired.value)
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().p3d_shearlet_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        if lib is not None:   # (module globals are gone while the interpreter shuts down: the process's device memory goes with it)
-            self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    _cube = Plan._cube
+    def _tau_shape(self):
+        return (self.nsh,)
 
     def transform(self, x):
         """(…, nil, nxl) -> (…, nil, nxl, nsh) complex64 (the reference's layout: shearlets on the last axis)."""
@@ -995,55 +867,12 @@ class ShearletPlan:
         check(lib().p3d_shearlet_inverse_c64(self.handle, _ptr(dev), _ptr(out), st.shape[0]))
         return out[0] if squeeze else out
 
-    def stats(self, x):
-        """(nslices, nsh, 5): Re/Im of the lexicographic (real cubes: signed) max, max |c|, min |c|, sum |c|^2 per shearlet."""
-        xc, dt = self._cube(x)
-        st = np.empty((xc.shape[0], self.nsh, 5), np.float64)
-        check(lib().p3d_shearlet_stats(self.handle, _ptr(xc), dt, xc.shape[0], _ptr(st)))
-        return st
-
-    def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
-        """tau: (nslices, niter, nsh) real or complex.  Returns (out, niter_done, sums, elapsed_ms)."""
-        xc, dt = self._cube(x)
-        n = xc.shape[0]
-        m = np.ascontiguousarray(mask, dtype=np.float32)
-        if m.shape != (self.nil, self.nxl):
-            raise ValueError(f"mask shape {m.shape} != {(self.nil, self.nxl)}")
-        tau = np.broadcast_to(np.asarray(tau), (n, niter, self.nsh))
-        t = np.empty(tau.shape + (2,), np.float64)
-        t[..., 0] = tau.real
-        t[..., 1] = tau.imag if np.iscomplexobj(tau) else 0.0
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
-        out = np.empty_like(xc)
-        done = np.zeros(n, np.int32)
-        sums = np.zeros((niter + 1, n), np.float64)
-        ms = C.c_double(0.0)
-        check(lib().p3d_shearlet_run(self.handle, _ptr(xc), dt, _ptr(m), _ptr(t), None if act is None else _ptr(act),
-                                     C.byref(prm), _ptr(out), n, _ptr(done), _ptr(sums), C.byref(ms)))
-        return out, done, sums, ms.value
-
     def stats_dev(self, x_ptr, dtype, n):
-        """`stats` for a cube resident on the device (raw pointer, P3D_C64 / P3D_F32)."""
+        """(nslices, nsh, 5): Re/Im of the lexicographic (real cubes: signed) max, max |c|, min |c|, sum |c|^2 per shearlet; raw pointer (host or
+        device), P3D_C64 / P3D_F32."""
         st = np.empty((n, self.nsh, 5), np.float64)
-        check(lib().p3d_shearlet_stats(self.handle, C.c_void_p(x_ptr), dtype, n, _ptr(st)))
+        check(lib().p3d_shearlet_stats(self.handle, x_ptr, dtype, n, _ptr(st)))
         return st
-
-    def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op="hard", version="regular", eps=0.0, alpha=1.0,
-                active=None):
-        """`run` on device-resident buffers (raw pointers).  Returns (niter_done, sums, device ms of the loop)."""
-        tau = np.broadcast_to(np.asarray(tau), (n, niter, self.nsh))
-        t = np.empty(tau.shape + (2,), np.float64)
-        t[..., 0] = tau.real
-        t[..., 1] = tau.imag if np.iscomplexobj(tau) else 0.0
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
-        done = np.zeros(n, np.int32)
-        sums = np.zeros((niter + 1, n), np.float64)
-        ms = C.c_double(0.0)
-        check(lib().p3d_shearlet_run(self.handle, C.c_void_p(x_ptr), dtype, C.c_void_p(mask_ptr), _ptr(t), None if act is None else _ptr(act),
-                                     C.byref(prm), C.c_void_p(out_ptr), n, _ptr(done), _ptr(sums), C.byref(ms)))
-        return done, sums, ms.value
 
 
 def shearlet64_fused_shape(nil, nxl):
@@ -1051,17 +880,14 @@ def shearlet64_fused_shape(nil, nxl):
     return bool(lib().p3d_shearlet64_fused_shape(int(nil), int(nxl)))
 
 
-class ShearletPlan64:
+class ShearletPlan64(_PlanBase64):
     """p3d_splan64 wrapper: the SHEARLET POCS loop in double precision (include/p3d.h) for complex128 / float64 cubes, and for complex64 /
-    float32 cubes on request (``precision='reference'``); ``psi`` (nil, nxl, nsh) as for :class:`ShearletPlan`, kept in double."""
-    _DT = WaveletPlan64._DT
+    float32 cubes on request (``precision='reference'``); ``psi`` (nil, nxl, nsh) as for :class:`ShearletPlan`, kept in double.
+    tau: (nslices, niter, nsh)."""
+    _DESTROY, _RUN = "p3d_shearlet64_plan_destroy", "p3d_shearlet64_run"
 
     def __init__(self, psi, max_slices=1, device=0):
-        psi = np.asarray(psi)
-        if psi.ndim != 3:
-            raise ValueError(f"Psi must be (nil, nxl, nshearlets), got shape {psi.shape}")
-        if np.iscomplexobj(psi):
-            raise NotImplementedError("complex shearlet spectra (realCoefficients=False) are not implemented")
+        psi = _real_psi(psi)
         self.nil, self.nxl, self.nsh = (int(v) for v in psi.shape)
         self.max_slices, self.device = int(max_slices), int(device)
         dev_psi = np.ascontiguousarray(np.moveaxis(psi, -1, 0), dtype=np.float64)
@@ -1074,58 +900,14 @@ class ShearletPlan64:
         self.paired = bool(fused.value & 2)  # ... and real cubes on Hermitian coefficient slices, two columns per transform (symmetric spectra, even extents)
         self.row_group_fraction = frac.value   # share of the (shearlet, row group) pairs those passes touch (rows off a spectrum's support are skipped)
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().p3d_shearlet64_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        if lib is not None:
-            self.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    _cube = WaveletPlan64._cube
-
-    def stats(self, x):
-        """(nslices, nsh, 5): Re / Im of the lexicographic (real cubes: signed) max, max |c|, min |c|, sum |c|^2 per shearlet, in double."""
-        xc, dt = self._cube(x)
-        return self.stats_dev(xc.ctypes.data, dt, xc.shape[0])
+    def _tau_shape(self):
+        return (self.nsh,)
 
     def stats_dev(self, x_ptr, dtype, n):
+        """(nslices, nsh, 5): Re / Im of the lexicographic (real cubes: signed) max, max |c|, min |c|, sum |c|^2 per shearlet, in double."""
         st = np.empty((n, self.nsh, 5), np.float64)
-        check(lib().p3d_shearlet64_stats(self.handle, C.c_void_p(x_ptr), dtype, n, _ptr(st)))
+        check(lib().p3d_shearlet64_stats(self.handle, x_ptr, dtype, n, _ptr(st)))
         return st
-
-    def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
-        """Host arrays in, host array out (dtype of ``x``).  tau: (nslices, niter, nsh) real or complex.  Returns (out, niter_done, sums, ms)."""
-        xc, dt = self._cube(x)
-        m = np.ascontiguousarray(mask, dtype=np.float64)
-        if m.shape != (self.nil, self.nxl):
-            raise ValueError(f"mask shape {m.shape} != {(self.nil, self.nxl)}")
-        out = np.empty_like(xc)
-        done, sums, ms = self.run_dev(xc.ctypes.data, dt, m.ctypes.data, tau, niter, out.ctypes.data, xc.shape[0], thresh_op=thresh_op, version=version,
-                                      eps=eps, alpha=alpha, active=active)
-        return out, done, sums, ms
-
-    def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
-        """`run` on raw pointers (host or device; the mask is DOUBLE [nil][nxl]).  Returns (niter_done, sums, device ms of the loop)."""
-        tau = np.broadcast_to(np.asarray(tau), (n, niter, self.nsh))
-        t = np.empty(tau.shape + (2,), np.float64)
-        t[..., 0] = tau.real
-        t[..., 1] = tau.imag if np.iscomplexobj(tau) else 0.0
-        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
-        done = np.zeros(n, np.int32)
-        sums = np.zeros((niter + 1, n), np.float64)
-        ms = C.c_double(0.0)
-        check(lib().p3d_shearlet64_run(self.handle, C.c_void_p(x_ptr), dtype, C.c_void_p(mask_ptr), _ptr(t), None if act is None else _ptr(act),
-                                       C.byref(prm), C.c_void_p(out_ptr), n, _ptr(done), _ptr(sums), C.byref(ms)))
-        return done, sums, ms.value
 
 
 def time2freq(x, dt, t0=0.0, nfft=None, real_only=False, window=None, device=0):
@@ -1785,7 +1567,7 @@ def multi_run(x, mask, tau, niter, devices, thresh_op="hard", version="regular",
     m = np.ascontiguousarray(mask, dtype=np.float32)
     if m.shape != (nil, nxl):
         raise ValueError(f"mask shape {m.shape} != {(nil, nxl)}")
-    t = Plan._tau(tau, n, niter)
+    t = _tau_table(tau, (n, niter))
     act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
     prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
     dev = np.ascontiguousarray(devices, dtype=np.int32)

@@ -347,7 +347,7 @@ struct p3d_plan {
     c32* tw32 = nullptr;                        // P32::build_tw
     int* flag = nullptr;                        // device int[2]: mask not binary / x non-zero at a missing trace
     unsigned* rowbase = nullptr;                // [nil+1] observed positions before each row
-    void* xc = nullptr;                         // compact observed samples [nslices][nobs]
+    char* xc = nullptr;                         // compact observed samples [nslices][nobs] (xc_cap: bytes)
     size_t xc_cap = 0;
     double* sums = nullptr;     // [(niter+1)][nslices]
     size_t sums_cap = 0;
@@ -1021,13 +1021,7 @@ int p3d_fft2_shrink_c64(p3d_plan* p, const void* in, const double* tau, int op, 
     P3D_TRY(hipSetDevice(p->device));
     const size_t bytes = sizeof(c32) * p->slice_elems() * nslices;
     if ((rc = ensure_staging(p, sizeof(c32) * p->slice_elems() * p->max_slices))) return rc;
-    if (p->tau_cap < (size_t)nslices) {
-        if (p->tau) hipFree(p->tau);
-        p->tau = nullptr;
-        p->tau_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * nslices));
-        p->tau_cap = nslices;
-    }
+    if ((rc = grow(p->tau, p->tau_cap, (size_t)nslices))) return rc;
     std::vector<c32> tau_f(nslices);
     for (int s = 0; s < nslices; ++s) tau_f[s] = tau_for_device(tau[2 * s], tau[2 * s + 1], op == P3D_OP_HARD);
     P3D_TRY(hipMemcpy(p->tau, tau_f.data(), sizeof(c32) * nslices, hipMemcpyHostToDevice));
@@ -1120,15 +1114,7 @@ static bool want_compact(p3d_plan* p, int nonbinary, unsigned nobs, int niter, c
 
 static int ensure_xc(p3d_plan* p, int nslices, unsigned nobs, int dtype)
 {
-    const size_t need = (size_t)nslices * nobs * (dtype == P3D_C64 ? sizeof(c32) : sizeof(float));
-    if (p->xc_cap < need) {
-        if (p->xc) hipFree(p->xc);
-        p->xc = nullptr;
-        p->xc_cap = 0;
-        P3D_TRY(hipMalloc(&p->xc, need));
-        p->xc_cap = need;
-    }
-    return P3D_OK;
+    return grow(p->xc, p->xc_cap, (size_t)nslices * nobs * (dtype == P3D_C64 ? sizeof(c32) : sizeof(float)));
 }
 
 int p3d_pocs_prime_dev(p3d_plan* p, const void* x, int dtype, const float* mask, int nslices, double* stats)
@@ -1241,190 +1227,121 @@ int p3d_pocs_stats(p3d_plan* p, const void* x, int dtype, int nslices, double* s
     return p3d_pocs_stats_dev(p, p->st_x, dtype, nslices, stats);
 }
 
-int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, const double* tau, const uint8_t* active,
-                     const p3d_pocs_params* prm, void* out, int nslices, int32_t* niter_done, double* sums,
-                     double* elapsed_ms)
+// What p3d_pocs_run_dev hands the loop it picks: the caller's arguments, what it derived from them and the frame of the loop (p3d_host.hpp),
+// begun -- schedule and state are on the device, the clock runs.
+struct RunJob {
+    p3d_plan* p;
+    const void* x;
+    int dtype;
+    const float* mask;
+    const double* tau;
+    const p3d_pocs_params* prm;
+    void* out;
+    int nslices;
+    int32_t* niter_done;
+    double* sums;
+    double* elapsed_ms;
+    int base_op;        // thresh_op without P3D_OP_PERCENTILE
+    bool percentile;
+    RunSwitches sw;
+    LoopFrame frame;
+};
+
+// unfused any-length pipeline: first input, then per iteration fft2 -> threshold -> ifft2 -> re-insertion
+static int run_generic(RunJob& j)
 {
-    // P3D_FLAG_PRIMED: the caller says p3d_pocs_prime_dev has just run on exactly this cube and mask -- believed only if the plan
-    // agrees (same pointers, type and batch, nothing else on the plan in between)
-    const bool primed_in = p && prm && (prm->flags & P3D_FLAG_PRIMED) && p->primed.valid && p->primed.x == x && p->primed.mask == mask &&
-                           p->primed.dtype == dtype && p->primed.nslices == nslices;
-    const p3d_plan::Primed primed_state = p ? p->primed : p3d_plan::Primed{};
-    int rc = check_batch(p, nslices);
-    if (rc) return rc;
-    if (!x || !mask || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
-    if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
-    if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
-    const bool percentile = (prm->thresh_op & P3D_OP_PERCENTILE) != 0;
-    const int base_op = prm->thresh_op & ~P3D_OP_PERCENTILE;
-    if (base_op < P3D_OP_HARD || base_op > P3D_OP_GARROTE)
-        return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented by the HIP kernels", prm->thresh_op);
-    if (prm->version < P3D_VER_REGULAR || prm->version > P3D_VER_ADAPTIVE)
-        return fail(P3D_ERR_INVALID, "unknown version %d", prm->version);
-    P3D_TRY(hipSetDevice(p->device));
-
-    const int niter = prm->niter;
-    const RunSwitches sw = read_switches();
-    const bool profile = (prm->flags & P3D_FLAG_PROFILE) != 0;
-    const bool early = prm->eps > 0.0;
-    const bool adaptive = prm->version == P3D_VER_ADAPTIVE;
-
-    // device-side schedule, state and cost accumulators
-    const size_t ntau = (size_t)nslices * niter;
-    if (p->tau_cap < ntau) {
-        if (p->tau) hipFree(p->tau);
-        p->tau = nullptr;
-        p->tau_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * ntau));
-        p->tau_cap = ntau;
-    }
-    const size_t nsum = (size_t)(niter + 1) * nslices;
-    if (p->sums_cap < nsum) {
-        if (p->sums) hipFree(p->sums);
-        p->sums = nullptr;
-        p->sums_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
-        p->sums_cap = nsum;
-    }
-    std::vector<c32> tau_f(ntau);
-    for (size_t i = 0; i < ntau; ++i) tau_f[i] = tau_for_device(tau[2 * i], tau[2 * i + 1], prm->thresh_op == P3D_OP_HARD);
-    std::vector<int> done_h(nslices, 0);
-    if (active)
-        for (int s = 0; s < nslices; ++s) done_h[s] = active[s] ? 0 : -1;
-    P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-
-    size_t nev = 0;
-    if (profile) {
-        const size_t need = 2 * (size_t)niter + 2;
-        while (p->prof_events.size() < need) {
-            hipEvent_t e;
-            P3D_TRY(hipEventCreate(&e));
-            p->prof_events.push_back(e);
+    p3d_plan* const p = j.p;
+    const p3d_pocs_params* const prm = j.prm;
+    const void* const x = j.x;
+    const float* const mask = j.mask;
+    const double* const tau = j.tau;
+    void* const out = j.out;
+    const int dtype = j.dtype, nslices = j.nslices, niter = prm->niter, base_op = j.base_op;
+    const bool percentile = j.percentile, early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE;
+    int rc;
+    const size_t per_slice = p->slice_elems();
+    const int* done_d = (early || j.frame.any_off()) ? p->done : nullptr;
+    P3D_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, nslices, per_slice,
+                              done_d, 0, p->stream));
+    for (int k = 0; k < niter; ++k) {
+        const bool last = k + 1 == niter;
+        if ((rc = gen_fft2(p, p->work, p->work, nslices, 0, done_d))) return rc;
+        if (percentile) {  // tau[s][k] <- np.percentile(|X_s|, perc_k): two order statistics + linear interpolation
+            std::vector<unsigned> sel_h((size_t)nslices * 16, 0u);
+            std::vector<float> frac_h(nslices);
+            for (int s = 0; s < nslices; ++s)
+                percentile_rank(tau[2 * ((size_t)s * niter + k)], per_slice, &sel_h[(size_t)s * 8], &sel_h[((size_t)nslices + s) * 8], &frac_h[s]);
+            P3D_TRY(hipMemcpyAsync(p->pct_sel, sel_h.data(), sizeof(unsigned) * sel_h.size(), hipMemcpyHostToDevice, p->stream));
+            P3D_TRY(hipMemcpyAsync(p->pct_frac, frac_h.data(), sizeof(float) * nslices, hipMemcpyHostToDevice, p->stream));
+            P3D_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * 2048 * (size_t)nslices, p->stream));
+            for (int which = 0; which < 2; ++which) {
+                unsigned* sel = p->pct_sel + (size_t)which * nslices * 8;
+                for (int level = 0; level < 3; ++level) {
+                    P3D_TRY(gen_launch_pct_hist(p->work, per_slice, sel, p->pct_hist, level, nslices, p->stream));
+                    P3D_TRY(gen_launch_pct_scan(sel, p->pct_hist, level, nslices, p->stream));
+                }
+            }
+            P3D_TRY(gen_launch_pct_tau(p->pct_sel, p->pct_sel + (size_t)nslices * 8, p->pct_frac, p->tau, niter, k, nslices, p->stream));
+            P3D_TRY(hipStreamSynchronize(p->stream));  // sel_h / frac_h are reused next iteration
         }
+        P3D_TRY(gen_launch_shrink(p->work, p->tau, niter, k, base_op, nslices, per_slice, done_d, p->stream));
+        if ((rc = gen_fft2(p, p->work, p->work, nslices, 1, done_d))) return rc;
+        P3D_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0,
+                                  (early || last) ? 1 : 0, (float)prm->alpha, nslices, per_slice, p->done, last ? 1 : 0, p->stream));
+        if (early) conv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
     }
+    P3D_TRY(hipGetLastError());
+    if ((rc = j.frame.enqueue_end(j.sums)) || (rc = j.frame.collect(j.niter_done, j.elapsed_ms))) return rc;
+    p->prof_col_n = p->prof_row_n = 0;
+    return P3D_OK;
+}
+
+// Small slices (32 ... 128 points per axis, at most 8192 per slice): the whole job in ONE kernel, a workgroup per slice, the
+// slice in registers and LDS for all iterations (p3d_resident.hip).  Bit-identical to the passes of run_fused, which stay for the
+// options it does not cover (APOCS, non-binary masks) and behind P3D_NO_RESIDENT=1.
+static int run_resident(RunJob& j)
+{
+    p3d_plan* const p = j.p;
+    const p3d_pocs_params* const prm = j.prm;
+    const void* const x = j.x;
+    void* const out = j.out;
+    const int dtype = j.dtype, nslices = j.nslices, niter = prm->niter, base_op = j.base_op;
+    int rc;
+    ResidentArgs ra{};
+    ra.x = x; ra.out = out; ra.bits = p->bits; ra.tau = p->tau; ra.done = p->done; ra.sums = p->sums;
+    ra.tw_row = p->tw_row; ra.tw_col = p->tw_col;
+    ra.nslices = nslices; ra.niter = niter; ra.op = base_op; ra.dtype = dtype;
+    ra.alpha = (float)prm->alpha; ra.scale = (float)(1.0 / ((double)p->nil * (double)p->nxl)); ra.eps = prm->eps;
+    P3D_TRY(resident_launch(p->nil, p->nxl, ra, p->stream));
+    if ((rc = j.frame.enqueue_end(j.sums)) || (rc = j.frame.collect(j.niter_done, j.elapsed_ms))) return rc;
+    p->last_nonzero_fraction = -1.0;
+    p->prof_col_n = p->prof_row_n = 0;
+    return P3D_OK;
+}
+
+// The fused two-pass loop: a row pass and a column pass per iteration on the tuned, flexible-length or mixed-radix kernels.  nonbinary / nobs: what
+// pack_mask (or the primed pass) found; primed_in / primed_state: p3d_pocs_prime_dev has just run on exactly this cube and mask.
+static int run_fused(RunJob& j, int nonbinary, unsigned nobs, bool primed_in, const p3d_plan::Primed& primed_state)
+{
+    p3d_plan* const p = j.p;
+    const p3d_pocs_params* const prm = j.prm;
+    const void* const x = j.x;
+    const float* const mask = j.mask;
+    const double* const tau = j.tau;
+    void* const out = j.out;
+    const int dtype = j.dtype, nslices = j.nslices, niter = prm->niter, base_op = j.base_op;
+    const bool percentile = j.percentile, early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE;
+    const RunSwitches& sw = j.sw;
+    double* const sums = j.sums;
+    std::vector<int>& done_h = j.frame.done_h;
+    const bool profile = (prm->flags & P3D_FLAG_PROFILE) != 0;
+    const bool flex_rows = is_flex(p->ops_row);   // the flexible row pass reads the float weights
+    int rc;
+    size_t nev = 0;
     auto stamp = [&]() -> hipError_t {
         if (!profile) return hipSuccess;
         return hipEventRecord(p->prof_events[nev++], p->stream);
     };
-
-    P3D_TRY(hipEventRecord(p->ev0, p->stream));
-
-    // The -percentile operators rank the moduli of the whole spectrum (np.percentile, POCS.py:43-57).  The fused passes can do it
-    // where the column-blocked work buffer holds exactly the slice (no padding columns): the column pass is split into forward
-    // transform | rank + threshold | inverse transform.  Otherwise:
-    const bool pct_fused = percentile && !p->generic && !sw.no_pct_fused && wk_slice_stride(p->nil, p->nxl) == p->slice_elems();
-    if (percentile && !p->generic && !pct_fused) {
-        // the tuned kernels never materialise the spectrum; ranking it needs the unfused pipeline -> a second, generic plan
-        if (!p->pct_plan) {
-            p3d_plan* q = nullptr;
-            const int prc = create_plan(&q, p->device, p->nil, p->nxl, p->max_slices, true);
-            if (prc) return prc;
-            p->pct_plan = q;
-        }
-        return p3d_pocs_run_dev(p->pct_plan, x, dtype, mask, tau, active, prm, out, nslices, niter_done, sums, elapsed_ms);
-    }
-    if (p->generic) {
-        // unfused any-length pipeline: first input, then per iteration fft2 -> threshold -> ifft2 -> re-insertion
-        const size_t per_slice = p->slice_elems();
-        bool any_off = early;
-        for (int s = 0; s < nslices; ++s) any_off = any_off || done_h[s] != 0;
-        const int* done_d = any_off ? p->done : nullptr;
-        P3D_TRY(hipEventRecord(p->ev0, p->stream));
-        P3D_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, nslices, per_slice,
-                                  done_d, 0, p->stream));
-        for (int k = 0; k < niter; ++k) {
-            const bool last = k + 1 == niter;
-            if ((rc = gen_fft2(p, p->work, p->work, nslices, 0, done_d))) return rc;
-            if (percentile) {  // tau[s][k] <- np.percentile(|X_s|, perc_k): two order statistics + linear interpolation
-                std::vector<unsigned> sel_h((size_t)nslices * 16, 0u);
-                std::vector<float> frac_h(nslices);
-                for (int s = 0; s < nslices; ++s) {
-                    const double perc = tau[2 * ((size_t)s * niter + k)];
-                    double pos = perc / 100.0 * (double)(per_slice - 1);
-                    if (!(pos >= 0.0)) pos = 0.0;
-                    if (pos > (double)(per_slice - 1)) pos = (double)(per_slice - 1);
-                    const double fl = std::floor(pos);
-                    sel_h[(size_t)s * 8] = (unsigned)fl;
-                    sel_h[((size_t)nslices + s) * 8] = (unsigned)std::min(fl + 1.0, (double)(per_slice - 1));
-                    frac_h[s] = (float)(pos - fl);
-                }
-                P3D_TRY(hipMemcpyAsync(p->pct_sel, sel_h.data(), sizeof(unsigned) * sel_h.size(), hipMemcpyHostToDevice, p->stream));
-                P3D_TRY(hipMemcpyAsync(p->pct_frac, frac_h.data(), sizeof(float) * nslices, hipMemcpyHostToDevice, p->stream));
-                P3D_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * 2048 * (size_t)nslices, p->stream));
-                for (int which = 0; which < 2; ++which) {
-                    unsigned* sel = p->pct_sel + (size_t)which * nslices * 8;
-                    for (int level = 0; level < 3; ++level) {
-                        P3D_TRY(gen_launch_pct_hist(p->work, per_slice, sel, p->pct_hist, level, nslices, p->stream));
-                        P3D_TRY(gen_launch_pct_scan(sel, p->pct_hist, level, nslices, p->stream));
-                    }
-                }
-                P3D_TRY(gen_launch_pct_tau(p->pct_sel, p->pct_sel + (size_t)nslices * 8, p->pct_frac, p->tau, niter, k, nslices, p->stream));
-                P3D_TRY(hipStreamSynchronize(p->stream));  // sel_h / frac_h are reused next iteration
-            }
-            P3D_TRY(gen_launch_shrink(p->work, p->tau, niter, k, base_op, nslices, per_slice, done_d, p->stream));
-            if ((rc = gen_fft2(p, p->work, p->work, nslices, 1, done_d))) return rc;
-            P3D_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0,
-                                      (early || last) ? 1 : 0, (float)prm->alpha, nslices, per_slice, p->done, last ? 1 : 0, p->stream));
-            if (early) conv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
-        }
-        P3D_TRY(hipGetLastError());
-        P3D_TRY(hipEventRecord(p->ev1, p->stream));
-        P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-        if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-        P3D_TRY(hipStreamSynchronize(p->stream));
-        if (niter_done)
-            for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
-        if (elapsed_ms) {
-            float ms = 0.f;
-            P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-            *elapsed_ms = ms;
-        }
-        p->prof_col_n = p->prof_row_n = 0;
-        return P3D_OK;
-    }
-
-    // packed trace mask: binary masks (the workflow's fold-derived mask, cube_POCS_interpolation_3D.py:242-244)
-    // travel as one 16-bit word per thread and row; anything else keeps the float weights
-    const bool flex_rows = is_flex(p->ops_row);   // the flexible row pass reads the float weights
-    int nonbinary = 0;
-    unsigned nobs = 0;
-    if (primed_in) {   // packed by p3d_pocs_prime_dev, still in place
-        nonbinary = primed_state.nonbinary;
-        nobs = primed_state.nobs;
-        P3D_TRY(hipMemsetAsync(p->flag, 0, 2 * sizeof(int), p->stream));
-    } else if ((rc = pack_mask(p, mask, &nonbinary, &nobs))) {
-        return rc;
-    }
-    if (sw.no_mask_bits) nonbinary = 1;  // experiments only
-
-    // Small slices (32 ... 128 points per axis, at most 8192 per slice): the whole job in ONE kernel, a workgroup per slice, the
-    // slice in registers and LDS for all iterations (p3d_resident.hip).  Bit-identical to the passes below, which stay for the
-    // options it does not cover (APOCS, non-binary masks) and behind P3D_NO_RESIDENT=1.
-    if (!nonbinary && !adaptive && !percentile && !sw.no_resident && !flex_rows && !is_flex(p->ops_col) && resident_supported(p->nil, p->nxl) &&
-        (size_t)p->nil * p->nxl <= RESIDENT_MAX_POINTS) {
-        ResidentArgs ra{};
-        ra.x = x; ra.out = out; ra.bits = p->bits; ra.tau = p->tau; ra.done = p->done; ra.sums = p->sums;
-        ra.tw_row = p->tw_row; ra.tw_col = p->tw_col;
-        ra.nslices = nslices; ra.niter = niter; ra.op = base_op; ra.dtype = dtype;
-        ra.alpha = (float)prm->alpha; ra.scale = (float)(1.0 / ((double)p->nil * (double)p->nxl)); ra.eps = prm->eps;
-        P3D_TRY(resident_launch(p->nil, p->nxl, ra, p->stream));
-        P3D_TRY(hipEventRecord(p->ev1, p->stream));
-        P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-        if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-        P3D_TRY(hipStreamSynchronize(p->stream));
-        if (niter_done)
-            for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
-        if (elapsed_ms) {
-            float ms = 0.f;
-            P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-            *elapsed_ms = ms;
-        }
-        p->last_nonzero_fraction = -1.0;
-        p->prof_col_n = p->prof_row_n = 0;
-        return P3D_OK;
-    }
     // Compact observed samples for the steady-state row pass: only the observed positions of x are non-zero in
     // the workflow (x = stacked traces, mask = fold >= 1); ROW_FIRST verifies that and the full cube is used if not.
     bool compact = want_compact(p, nonbinary, nobs, niter, sw);
@@ -1446,8 +1363,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     r.work = p->work;
     r.out = out;
     // the per-slice state array is only consulted when a slice can actually be switched off
-    bool any_off = early;
-    for (int s = 0; s < nslices; ++s) any_off = any_off || done_h[s] != 0;
+    const bool any_off = early || j.frame.any_off();
     r.sums = p->rowsum;
     r.done = any_off ? p->done : nullptr;
     r.dtype = dtype;
@@ -1559,15 +1475,8 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         pct_frac_h.assign((size_t)niter * nslices, 0.f);
         for (int k = 0; k < niter; ++k)
             for (int s = 0; s < nslices; ++s) {
-                const double perc = tau[2 * ((size_t)s * niter + k)];
-                double pos = perc / 100.0 * (double)(per_slice - 1);
-                if (!(pos >= 0.0)) pos = 0.0;
-                if (pos > (double)(per_slice - 1)) pos = (double)(per_slice - 1);
-                const double fl = std::floor(pos);
                 unsigned* sel = &pct_sel_h[(size_t)k * nslices * 16];
-                sel[(size_t)s * 8] = (unsigned)fl;
-                sel[((size_t)nslices + s) * 8] = (unsigned)std::min(fl + 1.0, (double)(per_slice - 1));
-                pct_frac_h[(size_t)k * nslices + s] = (float)(pos - fl);
+                percentile_rank(tau[2 * ((size_t)s * niter + k)], per_slice, &sel[(size_t)s * 8], &sel[((size_t)nslices + s) * 8], &pct_frac_h[(size_t)k * nslices + s]);
             }
         P3D_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * 2048 * (size_t)nslices, p->stream));
     }
@@ -1696,22 +1605,11 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         }
     }
     P3D_TRY(hipGetLastError());
-    P3D_TRY(hipEventRecord(p->ev1, p->stream));
-
-    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+    if ((rc = j.frame.enqueue_end(sums))) return rc;
     unsigned long long kept_blocks = 0;
     if (sparse) P3D_TRY(hipMemcpyAsync(&kept_blocks, p->nzcount, sizeof kept_blocks, hipMemcpyDeviceToHost, p->stream));
-    P3D_TRY(hipStreamSynchronize(p->stream));
+    if ((rc = j.frame.collect(j.niter_done, j.elapsed_ms))) return rc;
     if (sparse) p->last_nonzero_fraction = (double)kept_blocks / ((double)niter * nslices * (real_path ? (n2_work + 7) / 8 : nblocks));
-
-    if (niter_done)
-        for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
-    if (elapsed_ms) {
-        float ms = 0.f;
-        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-        *elapsed_ms = ms;
-    }
     if (profile) {
         p->prof_col_ms = p->prof_row_ms = 0;
         p->prof_col_n = p->prof_row_n = 0;
@@ -1728,6 +1626,85 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         }
     }
     return P3D_OK;
+}
+
+int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, const double* tau, const uint8_t* active,
+                     const p3d_pocs_params* prm, void* out, int nslices, int32_t* niter_done, double* sums,
+                     double* elapsed_ms)
+{
+    // P3D_FLAG_PRIMED: the caller says p3d_pocs_prime_dev has just run on exactly this cube and mask -- believed only if the plan
+    // agrees (same pointers, type and batch, nothing else on the plan in between)
+    const bool primed_in = p && prm && (prm->flags & P3D_FLAG_PRIMED) && p->primed.valid && p->primed.x == x && p->primed.mask == mask &&
+                           p->primed.dtype == dtype && p->primed.nslices == nslices;
+    const p3d_plan::Primed primed_state = p ? p->primed : p3d_plan::Primed{};
+    int rc = check_batch(p, nslices);
+    if (rc) return rc;
+    if (!x || !mask || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
+    const bool percentile = (prm->thresh_op & P3D_OP_PERCENTILE) != 0;
+    const int base_op = prm->thresh_op & ~P3D_OP_PERCENTILE;
+    if (base_op < P3D_OP_HARD || base_op > P3D_OP_GARROTE)
+        return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented by the HIP kernels", prm->thresh_op);
+    if (prm->version < P3D_VER_REGULAR || prm->version > P3D_VER_ADAPTIVE)
+        return fail(P3D_ERR_INVALID, "unknown version %d", prm->version);
+    P3D_TRY(hipSetDevice(p->device));
+
+    const int niter = prm->niter;
+    const RunSwitches sw = read_switches();
+    const bool profile = (prm->flags & P3D_FLAG_PROFILE) != 0;
+
+    // device-side schedule, state and cost accumulators
+    const size_t ntau = (size_t)nslices * niter;
+    if ((rc = grow(p->tau, p->tau_cap, ntau)) || (rc = grow(p->sums, p->sums_cap, (size_t)(niter + 1) * nslices))) return rc;
+    std::vector<c32> tau_f(ntau);
+    for (size_t i = 0; i < ntau; ++i) tau_f[i] = tau_for_device(tau[2 * i], tau[2 * i + 1], prm->thresh_op == P3D_OP_HARD);
+    if (profile) {
+        const size_t need = 2 * (size_t)niter + 2;
+        while (p->prof_events.size() < need) {
+            hipEvent_t e;
+            P3D_TRY(hipEventCreate(&e));
+            p->prof_events.push_back(e);
+        }
+    }
+    RunJob j{p, x, dtype, mask, tau, prm, out, nslices, niter_done, sums, elapsed_ms, base_op, percentile, sw, LoopFrame(p, active, nslices, niter)};
+    P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
+    if ((rc = j.frame.begin())) return rc;
+
+    // The -percentile operators rank the moduli of the whole spectrum (np.percentile, POCS.py:43-57).  The fused passes can do it
+    // where the column-blocked work buffer holds exactly the slice (no padding columns): the column pass is split into forward
+    // transform | rank + threshold | inverse transform.  Otherwise:
+    const bool pct_fused = percentile && !p->generic && !sw.no_pct_fused && wk_slice_stride(p->nil, p->nxl) == p->slice_elems();
+    if (percentile && !p->generic && !pct_fused) {
+        // the tuned kernels never materialise the spectrum; ranking it needs the unfused pipeline -> a second, generic plan
+        if (!p->pct_plan) {
+            p3d_plan* q = nullptr;
+            const int prc = create_plan(&q, p->device, p->nil, p->nxl, p->max_slices, true);
+            if (prc) return prc;
+            p->pct_plan = q;
+        }
+        return p3d_pocs_run_dev(p->pct_plan, x, dtype, mask, tau, active, prm, out, nslices, niter_done, sums, elapsed_ms);
+    }
+    if (p->generic) return run_generic(j);
+
+    // packed trace mask: binary masks (the workflow's fold-derived mask, cube_POCS_interpolation_3D.py:242-244)
+    // travel as one 16-bit word per thread and row; anything else keeps the float weights
+    int nonbinary = 0;
+    unsigned nobs = 0;
+    if (primed_in) {   // packed by p3d_pocs_prime_dev, still in place
+        nonbinary = primed_state.nonbinary;
+        nobs = primed_state.nobs;
+        P3D_TRY(hipMemsetAsync(p->flag, 0, 2 * sizeof(int), p->stream));
+    } else if ((rc = pack_mask(p, mask, &nonbinary, &nobs))) {
+        return rc;
+    }
+    if (sw.no_mask_bits) nonbinary = 1;  // experiments only
+
+    const bool adaptive = prm->version == P3D_VER_ADAPTIVE;
+    if (!nonbinary && !adaptive && !percentile && !sw.no_resident && !is_flex(p->ops_row) && !is_flex(p->ops_col) && resident_supported(p->nil, p->nxl) &&
+        (size_t)p->nil * p->nxl <= RESIDENT_MAX_POINTS)
+        return run_resident(j);
+    return run_fused(j, nonbinary, nobs, primed_in, primed_state);
 }
 
 int p3d_pocs_run(p3d_plan* p, const void* x, int dtype, const float* mask, const double* tau, const uint8_t* active,

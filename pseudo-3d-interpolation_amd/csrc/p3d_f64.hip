@@ -29,6 +29,11 @@
 
 using p3d::fail;
 using p3d::use_device;
+using p3d::choose_out;
+using p3d::elem_bytes;
+using p3d::grow;
+using p3d::LoopFrame;
+using p3d::take_x;
 
 namespace {
 
@@ -793,19 +798,6 @@ int row_pass64(p3d_plan64* p, int dtype, double* sums_row, int adaptive, int wri
     return P3D_OK;
 }
 
-size_t esize(int dtype) { return dtype == P3D_C128 ? 16 : (dtype == P3D_F64 || dtype == P3D_C64 ? 8 : 4); }
-
-// a pointer into the memory of the plan's own device (the entry points take host or device pointers)
-bool on_plan_device(const p3d_plan64* p, const void* ptr)
-{
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
-        (void)hipGetLastError();   // ordinary host memory
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == p->device;
-}
-
 int check64(p3d_plan64* p, int nslices, int dtype)
 {
     if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
@@ -935,12 +927,7 @@ int p3d_pocs64_stats(p3d_plan64* p, const void* x, int dtype, int nslices, doubl
     int rc = check64(p, nslices, dtype);
     if (rc) return rc;
     if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
-    if (on_plan_device(p, x)) {
-        p->cur_x = x;
-    } else {
-        P3D_TRY(hipMemcpyAsync(p->st_x, x, esize(dtype) * p->per() * nslices, hipMemcpyDefault, p->stream));
-        p->cur_x = p->st_x;
-    }
+    if ((rc = take_x(p, x, elem_bytes(dtype) * p->per() * nslices))) return rc;
     p->cur_out = p->st_out;
     p->sparse = false;
     const int nblocks = p->fused ? p->tiles_col() : p3d_plan64::BLOCKS;
@@ -985,40 +972,17 @@ int p3d_pocs64_run(p3d_plan64* p, const void* x, int dtype, const double* mask, 
     const int niter = prm->niter;
     const bool early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE;
     const size_t ntau = (size_t)nslices * niter, nsum = (size_t)(niter + 1) * nslices, per = p->per();
-    if (p->tau_cap < ntau) {
-        if (p->tau) hipFree(p->tau);
-        p->tau = nullptr; p->tau_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c64) * ntau));
-        p->tau_cap = ntau;
-    }
-    if (p->sums_cap < nsum) {
-        if (p->sums) hipFree(p->sums);
-        p->sums = nullptr; p->sums_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
-        p->sums_cap = nsum;
-    }
-    std::vector<int> done_h(nslices, 0);
-    bool any_off = early;
-    if (active) for (int s = 0; s < nslices; ++s) { done_h[s] = active[s] ? 0 : -1; any_off = any_off || !active[s]; }
-    const int* done_d = any_off ? p->done : nullptr;
+    if ((rc = grow(p->tau, p->tau_cap, ntau)) || (rc = grow(p->sums, p->sums_cap, nsum))) return rc;
+    LoopFrame frame(p, active, nslices, niter);
+    const int* done_d = (early || frame.any_off()) ? p->done : nullptr;
     // the caller's own device buffers where it passed such (no staging copies: 80 bytes per point and two passes less for a resident batch);
     // a result buffer that overlaps the observed cube -- read in every iteration -- goes through the staging buffer
-    const size_t cube_bytes = esize(dtype) * per * nslices;
-    if (on_plan_device(p, x)) {
-        p->cur_x = x;
-    } else {
-        P3D_TRY(hipMemcpyAsync(p->st_x, x, cube_bytes, hipMemcpyDefault, p->stream));
-        p->cur_x = p->st_x;
-    }
-    const char* const xb = static_cast<const char*>(x);
-    char* const ob = static_cast<char*>(out);
-    const bool direct_out = on_plan_device(p, out) && (ob + cube_bytes <= xb || xb + cube_bytes <= ob);
-    p->cur_out = direct_out ? out : p->st_out;
+    const size_t cube_bytes = elem_bytes(dtype) * per * nslices;
+    if ((rc = take_x(p, x, cube_bytes))) return rc;
+    const bool direct_out = choose_out(p, x, out, cube_bytes);
     P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * per, hipMemcpyDefault, p->stream));
     P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));   // (Re, Im) pairs of doubles: c64's layout
-    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    P3D_TRY(hipEventRecord(p->ev0, p->stream));
+    if ((rc = frame.begin())) return rc;
     p->sparse = p->nzflag != nullptr;   // (tiles of the spectrum that the threshold empties are neither transformed back, stored nor read again: exact)
     if (p->fused) {
         // two kernels per iteration: rows (inverse transform, re-insertion, forward transform), columns (forward, threshold, inverse)
@@ -1046,18 +1010,9 @@ int p3d_pocs64_run(p3d_plan64* p, const void* x, int dtype, const double* mask, 
     }
     }
     P3D_TRY(hipGetLastError());
-    P3D_TRY(hipEventRecord(p->ev1, p->stream));
-    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+    if ((rc = frame.enqueue_end(sums))) return rc;
     if (!direct_out) P3D_TRY(hipMemcpyAsync(out, p->st_out, cube_bytes, hipMemcpyDefault, p->stream));
-    P3D_TRY(hipStreamSynchronize(p->stream));
-    if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
-    if (elapsed_ms) {
-        float ms = 0.f;
-        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-        *elapsed_ms = ms;
-    }
-    return P3D_OK;
+    return frame.collect(niter_done, elapsed_ms);
 }
 
 // test hook: batched fft2 / ifft2 (numpy.fft conventions) of HOST complex128 slices THROUGH THE LOOP'S OWN PASSES -- forward = the first row pass

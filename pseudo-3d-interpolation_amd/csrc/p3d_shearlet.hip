@@ -26,6 +26,8 @@
 
 using p3d::c32;
 using p3d::fail;
+using p3d::grow;
+using p3d::LoopFrame;
 
 namespace {
 
@@ -394,12 +396,7 @@ int p3d_shearlet_stats(p3d_splan* p, const void* x, int dtype, int nslices, doub
     // returns, and the plan's stream does not wait for the null stream -- the kernels below would read st_x early (seen as wrong statistics
     // when several processes share the GPU)
     P3D_TRY(hipMemcpyAsync(p->st_x, x, esz * p->per() * nslices, hipMemcpyDefault, p->stream));
-    if (p->sums_cap < (size_t)nslices) {
-        if (p->sums) hipFree(p->sums);
-        p->sums = nullptr; p->sums_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * 2 * p->max_slices));
-        p->sums_cap = 2 * (size_t)p->max_slices;
-    }
+    if (p->sums_cap < (size_t)nslices) S_RC(grow(p->sums, p->sums_cap, 2 * (size_t)p->max_slices));
     P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nslices, p->stream));
     supdate_kernel<<<dim3(blocks_for(p->per(), 256), nslices), 256, 0, p->stream>>>(nullptr, p->feed, p->st_x, dtype, nullptr, nullptr, p->sums, 0, 0, 0, 1.0f,
                                                                                   p->per(), nullptr, 0);
@@ -434,31 +431,18 @@ int p3d_shearlet_run(p3d_splan* p, const void* x, int dtype, const float* mask, 
     const bool early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE, real_only = dtype == P3D_F32;
     const size_t per = p->per(), esz = real_only ? sizeof(float) : sizeof(c32);
     const size_t ntau = (size_t)nslices * niter * nsh, nsum = (size_t)(niter + 1) * nslices;
-    if (p->tau_cap < ntau) {
-        if (p->tau) hipFree(p->tau);
-        p->tau = nullptr; p->tau_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * ntau));
-        p->tau_cap = ntau;
-    }
-    if (p->sums_cap < nsum) {
-        if (p->sums) hipFree(p->sums);
-        p->sums = nullptr; p->sums_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
-        p->sums_cap = nsum;
-    }
+    S_RC(grow(p->tau, p->tau_cap, ntau));
+    S_RC(grow(p->sums, p->sums_cap, nsum));
     std::vector<c32> tau_f(ntau);
     for (size_t i = 0; i < ntau; ++i) {
         tau_f[i] = p3d::tau_for_device(tau[2 * i], tau[2 * i + 1], prm->thresh_op == P3D_OP_HARD);
         if (real_only && tau[2 * i + 1] != 0.0) return fail(P3D_ERR_INVALID, "complex thresholds need a complex64 cube");
     }
-    std::vector<int> done_h(nslices, 0);
-    if (active) for (int s = 0; s < nslices; ++s) done_h[s] = active[s] ? 0 : -1;
+    LoopFrame frame(p, active, nslices, niter);
     P3D_TRY(hipMemcpyAsync(p->st_x, x, esz * per * nslices, hipMemcpyDefault, p->stream));   // x, mask, out: host or device pointers (on the plan's stream, see p3d_shearlet_stats)
     P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(float) * per, hipMemcpyDefault, p->stream));
     P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    P3D_TRY(hipEventRecord(p->ev0, p->stream));
+    S_RC(frame.begin());
     const dim3 ugrid(blocks_for(per, 256), nslices);
     supdate_kernel<<<ugrid, 256, 0, p->stream>>>(nullptr, p->feed, p->st_x, dtype, p->mask, p->st_out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, per,
                                                 p->done, 0);
@@ -485,18 +469,10 @@ int p3d_shearlet_run(p3d_splan* p, const void* x, int dtype, const float* mask, 
         if (early) sconv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
     }
     P3D_TRY(hipGetLastError());
-    P3D_TRY(hipEventRecord(p->ev1, p->stream));
-    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-    P3D_TRY(hipStreamSynchronize(p->stream));
+    S_RC(frame.enqueue_end(sums));
+    S_RC(frame.collect(niter_done, elapsed_ms));
     P3D_TRY(hipMemcpyAsync(out, p->st_out, esz * per * nslices, hipMemcpyDefault, p->stream));
     P3D_TRY(hipStreamSynchronize(p->stream));   // (the caller may read `out` on any stream once this returns)
-    if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
-    if (elapsed_ms) {
-        float ms = 0.f;
-        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-        *elapsed_ms = ms;
-    }
     return P3D_OK;
 }
 

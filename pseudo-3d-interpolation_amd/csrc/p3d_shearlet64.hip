@@ -29,6 +29,12 @@
 #include "p3d_internal.hpp"
 
 using p3d::fail;
+using p3d::elem_bytes;
+using p3d::grow;
+using p3d::LoopFrame;
+using p3d::on_plan_device;
+using p3d::real_dtype;
+using p3d::take_x;
 
 namespace {
 
@@ -313,48 +319,12 @@ struct p3d_splan64 {
 
 namespace {
 
-bool on_plan_device(const p3d_splan64* p, const void* ptr)
-{
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
-        (void)hipGetLastError();   // ordinary host memory
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == p->device;
-}
-
-size_t elem_bytes(int dtype) { return dtype == P3D_C128 ? 16 : (dtype == P3D_F64 || dtype == P3D_C64) ? 8 : 4; }
-bool real_dtype(int dtype) { return dtype == P3D_F64 || dtype == P3D_F32; }
-
 int s_check(p3d_splan64* p, int nslices, int dtype)
 {
     if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
     if (nslices < 1 || nslices > p->max_slices) return fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
     if (dtype != P3D_C64 && dtype != P3D_F32 && dtype != P3D_C128 && dtype != P3D_F64) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
     P3D_TRY(hipSetDevice(p->device));
-    return P3D_OK;
-}
-
-int ensure_sums(p3d_splan64* p, size_t n)
-{
-    if (p->sums_cap < n) {
-        if (p->sums) hipFree(p->sums);
-        p->sums = nullptr; p->sums_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * n));
-        p->sums_cap = n;
-    }
-    return P3D_OK;
-}
-
-// x (host or device) -> cur_x: the caller's own device buffer where it passed one, the staging buffer otherwise
-int take_x(p3d_splan64* p, const void* x, int dtype, int nslices)
-{
-    if (on_plan_device(p, x)) {
-        p->cur_x = x;
-    } else {
-        P3D_TRY(hipMemcpyAsync(p->st_x, x, elem_bytes(dtype) * p->per() * nslices, hipMemcpyDefault, p->stream));
-        p->cur_x = p->st_x;
-    }
     return P3D_OK;
 }
 
@@ -513,9 +483,9 @@ int p3d_shearlet64_stats(p3d_splan64* p, const void* x, int dtype, int nslices, 
 {
     S_RC(s_check(p, nslices, dtype));
     if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
-    S_RC(take_x(p, x, dtype, nslices));
+    S_RC(take_x(p, x, elem_bytes(dtype) * p->per() * nslices));
     if (p->pf) {
-        S_RC(ensure_sums(p, (size_t)nslices));
+        S_RC(grow(p->sums, p->sums_cap, (size_t)nslices));
         p3d::plan64_bind(p->pf, p->cur_x, nullptr);
         S_RC(p3d::plan64_shear_first(p->pf, dtype, p->sums, 0, 1.0, nslices, nullptr));
         const int pair = (p->pair && real_dtype(dtype)) ? 1 : 0;
@@ -549,23 +519,15 @@ int p3d_shearlet64_run(p3d_splan64* p, const void* x, int dtype, const double* m
     if (real_only)
         for (size_t i = 0; i < ntau; ++i)
             if (tau[2 * i + 1] != 0.0) return fail(P3D_ERR_INVALID, "complex thresholds need a complex cube");
-    if (p->tau_cap < ntau) {
-        if (p->tau) hipFree(p->tau);
-        p->tau = nullptr; p->tau_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c64) * ntau));
-        p->tau_cap = ntau;
-    }
-    S_RC(ensure_sums(p, nsum));
-    std::vector<int> done_h(nslices, 0);
-    if (active) for (int s = 0; s < nslices; ++s) done_h[s] = active[s] ? 0 : -1;
-    S_RC(take_x(p, x, dtype, nslices));
-    const bool direct_out = on_plan_device(p, out);
+    S_RC(grow(p->tau, p->tau_cap, ntau));
+    S_RC(grow(p->sums, p->sums_cap, nsum));
+    LoopFrame frame(p, active, nslices, niter);
+    S_RC(take_x(p, x, elem_bytes(dtype) * per * nslices));
+    const bool direct_out = on_plan_device(p, out);   // (no overlap test here, unlike choose_out)
     p->cur_out = direct_out ? out : p->st_out;
     P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * per, hipMemcpyDefault, p->stream));
     P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    P3D_TRY(hipEventRecord(p->ev0, p->stream));
+    S_RC(frame.begin());
     if (p->pf) {
         const double scale = 1.0 / ((double)p->nil * p->nxl);
         const int pair = (p->pair && real_only) ? 1 : 0, rows = pair ? p->nil / 2 + 1 : 0;
@@ -600,18 +562,9 @@ int p3d_shearlet64_run(p3d_splan64* p, const void* x, int dtype, const double* m
         }
     }
     P3D_TRY(hipGetLastError());
-    P3D_TRY(hipEventRecord(p->ev1, p->stream));
-    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
+    S_RC(frame.enqueue_end(sums));
     if (!direct_out) P3D_TRY(hipMemcpyAsync(out, p->st_out, elem_bytes(dtype) * per * nslices, hipMemcpyDefault, p->stream));
-    P3D_TRY(hipStreamSynchronize(p->stream));   // (the caller may read `out` on any stream once this returns)
-    if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
-    if (elapsed_ms) {
-        float ms = 0.f;
-        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-        *elapsed_ms = ms;
-    }
-    return P3D_OK;
+    return frame.collect(niter_done, elapsed_ms);   // (synchronises: the caller may read `out` on any stream once this returns)
 }
 
 }  // extern "C"

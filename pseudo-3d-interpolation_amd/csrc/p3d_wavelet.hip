@@ -30,6 +30,11 @@
 
 using p3d::fail;
 using p3d::use_device;
+using p3d::choose_out;
+using p3d::elem_bytes;
+using p3d::grow;
+using p3d::LoopFrame;
+using p3d::take_x;
 using p3d::c32;
 
 namespace {
@@ -1660,17 +1665,6 @@ static int w_inverse(p3d_wplan* p, int ns)
     return P3D_OK;
 }
 
-// a pointer into the memory of the plan's own device (the entry points take host or device pointers)
-static bool on_plan_device(const p3d_wplan* p, const void* ptr)
-{
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
-        (void)hipGetLastError();   // ordinary host memory
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == p->device;
-}
-
 static int w_check(p3d_wplan* p, int nslices, int dtype)
 {
     if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
@@ -1817,19 +1811,8 @@ int p3d_wavelet_stats(p3d_wplan* p, const void* x, int dtype, int nslices, doubl
     int rc = w_check(p, nslices, dtype);
     if (rc) return rc;
     if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
-    const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
-    if (on_plan_device(p, x)) {
-        p->cur_x = x;
-    } else {
-        P3D_TRY(hipMemcpyAsync(p->st_x, x, esz * p->per() * nslices, hipMemcpyDefault, p->stream));   // (ordered with the plan's stream: p3d_wavelet_run)
-        p->cur_x = p->st_x;
-    }
-    if (p->sums_cap < (size_t)nslices) {
-        if (p->sums) hipFree(p->sums);
-        p->sums = nullptr; p->sums_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * 2 * p->max_slices));
-        p->sums_cap = 2 * (size_t)p->max_slices;
-    }
+    if ((rc = take_x(p, x, elem_bytes(dtype) * p->per() * nslices))) return rc;   // (ordered with the plan's stream: p3d_wavelet_run)
+    if (p->sums_cap < (size_t)nslices && (rc = grow(p->sums, p->sums_cap, 2 * (size_t)p->max_slices))) return rc;
     P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nslices, p->stream));
     if ((rc = dtype == P3D_F32 ? w_stats<float>(p, dtype, nslices) : w_stats<c32>(p, dtype, nslices))) return rc;
     std::vector<float> host((size_t)nslices * p->nlev * 12);
@@ -1850,20 +1833,8 @@ int p3d_wavelet_run(p3d_wplan* p, const void* x, int dtype, const float* mask, c
     if (prm->thresh_op < P3D_OP_HARD || prm->thresh_op > P3D_OP_GARROTE)
         return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the wavelet transform", prm->thresh_op);
     const int niter = prm->niter;
-    const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
     const size_t ntau = (size_t)nslices * niter * p->nlev * 3, nsum = (size_t)(niter + 1) * nslices;
-    if (p->tau_cap < ntau) {
-        if (p->tau) hipFree(p->tau);
-        p->tau = nullptr; p->tau_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c32) * ntau));
-        p->tau_cap = ntau;
-    }
-    if (p->sums_cap < nsum) {
-        if (p->sums) hipFree(p->sums);
-        p->sums = nullptr; p->sums_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * nsum));
-        p->sums_cap = nsum;
-    }
+    if ((rc = grow(p->tau, p->tau_cap, ntau)) || (rc = grow(p->sums, p->sums_cap, nsum))) return rc;
     std::vector<c32> tau_f(ntau);
     bool real_tau = true;
     for (size_t i = 0; i < ntau; ++i) {
@@ -1872,20 +1843,10 @@ int p3d_wavelet_run(p3d_wplan* p, const void* x, int dtype, const float* mask, c
     }
     // float32 cubes with real thresholds stay real through the whole loop (what PyWavelets does for real input)
     const bool real_path = dtype == P3D_F32 && real_tau;
-    std::vector<int> done_h(nslices, 0);
-    if (active) for (int s = 0; s < nslices; ++s) done_h[s] = active[s] ? 0 : -1;
-    const size_t cube_bytes = esz * p->per() * nslices;
-    if (on_plan_device(p, x)) {
-        p->cur_x = x;
-    } else {
-        P3D_TRY(hipMemcpyAsync(p->st_x, x, cube_bytes, hipMemcpyDefault, p->stream));
-        p->cur_x = p->st_x;
-    }
-    // (the loop reads the observed cube in every iteration: a result buffer that overlaps it goes through the staging buffer)
-    const char* const xb = static_cast<const char*>(x);
-    char* const ob = static_cast<char*>(out);
-    const bool direct_out = on_plan_device(p, out) && (ob + cube_bytes <= xb || xb + cube_bytes <= ob);
-    p->cur_out = direct_out ? out : p->st_out;
+    LoopFrame frame(p, active, nslices, niter);
+    const size_t cube_bytes = elem_bytes(dtype) * p->per() * nslices;
+    if ((rc = take_x(p, x, cube_bytes))) return rc;
+    const bool direct_out = choose_out(p, x, out, cube_bytes);
     // the mask may be a device pointer: a device-to-device hipMemcpy runs on the null stream, need not have finished when it returns, and the plan's
     // (non-blocking) stream does not wait for it -- every copy of this entry point goes onto the plan's stream
     P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(float) * p->per(), hipMemcpyDefault, p->stream));
@@ -1899,23 +1860,12 @@ int p3d_wavelet_run(p3d_wplan* p, const void* x, int dtype, const float* mask, c
         P3D_TRY(hipStreamSynchronize(p->stream));
     }
     P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    P3D_TRY(hipEventRecord(p->ev0, p->stream));
+    if ((rc = frame.begin())) return rc;
     if ((rc = real_path ? w_loop<float>(p, dtype, nslices, prm) : w_loop<c32>(p, dtype, nslices, prm))) return rc;
-    P3D_TRY(hipEventRecord(p->ev1, p->stream));
-    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-    P3D_TRY(hipStreamSynchronize(p->stream));
+    if ((rc = frame.enqueue_end(sums)) || (rc = frame.collect(niter_done, elapsed_ms))) return rc;
     if (!direct_out) {
         P3D_TRY(hipMemcpyAsync(out, p->st_out, cube_bytes, hipMemcpyDefault, p->stream));
         P3D_TRY(hipStreamSynchronize(p->stream));
-    }
-    if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
-    if (elapsed_ms) {
-        float ms = 0.f;
-        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-        *elapsed_ms = ms;
     }
     return P3D_OK;
 }

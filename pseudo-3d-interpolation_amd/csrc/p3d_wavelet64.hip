@@ -25,6 +25,12 @@
 
 using p3d::fail;
 using p3d::use_device;
+using p3d::choose_out;
+using p3d::elem_bytes;
+using p3d::grow;
+using p3d::LoopFrame;
+using p3d::real_dtype;
+using p3d::take_x;
 
 namespace {
 
@@ -497,36 +503,12 @@ static int w_inverse(p3d_wplan64* p, int ns, const int* done)
     return P3D_OK;
 }
 
-static bool on_plan_device(const p3d_wplan64* p, const void* ptr)
-{
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
-        (void)hipGetLastError();   // ordinary host memory
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == p->device;
-}
-
-static size_t elem_bytes(int dtype) { return dtype == P3D_C128 ? 16 : (dtype == P3D_F64 || dtype == P3D_C64) ? 8 : 4; }
-static bool real_dtype(int dtype) { return dtype == P3D_F64 || dtype == P3D_F32; }
-
 static int w_check(p3d_wplan64* p, int nslices, int dtype)
 {
     if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
     if (nslices < 1 || nslices > p->max_slices) return fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
     if (dtype != P3D_C64 && dtype != P3D_F32 && dtype != P3D_C128 && dtype != P3D_F64) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
     P3D_TRY(hipSetDevice(p->device));
-    return P3D_OK;
-}
-
-static int ensure_sums(p3d_wplan64* p, size_t n)
-{
-    if (p->sums_cap < n) {
-        if (p->sums) hipFree(p->sums);
-        p->sums = nullptr; p->sums_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->sums, sizeof(double) * n));
-        p->sums_cap = n;
-    }
     return P3D_OK;
 }
 
@@ -579,12 +561,7 @@ int p3d_wavelet64_stats(p3d_wplan64* p, const void* x, int dtype, int nslices, d
     int rc = w_check(p, nslices, dtype);
     if (rc) return rc;
     if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
-    if (on_plan_device(p, x)) {
-        p->cur_x = x;
-    } else {
-        P3D_TRY(hipMemcpyAsync(p->st_x, x, elem_bytes(dtype) * p->per() * nslices, hipMemcpyDefault, p->stream));
-        p->cur_x = p->st_x;
-    }
+    if ((rc = take_x(p, x, elem_bytes(dtype) * p->per() * nslices))) return rc;
     if ((rc = real_dtype(dtype) ? w_stats<double>(p, dtype, nslices) : w_stats<c64>(p, dtype, nslices))) return rc;
     P3D_TRY(hipMemcpyAsync(stats, p->stats, sizeof(double) * (size_t)nslices * p->nlev * 12, hipMemcpyDeviceToHost, p->stream));
     P3D_TRY(hipStreamSynchronize(p->stream));
@@ -604,51 +581,24 @@ int p3d_wavelet64_run(p3d_wplan64* p, const void* x, int dtype, const double* ma
         return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented for the wavelet transform", prm->thresh_op);
     const int niter = prm->niter;
     const size_t ntau = (size_t)nslices * niter * p->nlev * 3, nsum = (size_t)(niter + 1) * nslices;
-    if (p->tau_cap < ntau) {
-        if (p->tau) hipFree(p->tau);
-        p->tau = nullptr; p->tau_cap = 0;
-        P3D_TRY(hipMalloc((void**)&p->tau, sizeof(c64) * ntau));
-        p->tau_cap = ntau;
-    }
-    if ((rc = ensure_sums(p, nsum))) return rc;
+    if ((rc = grow(p->tau, p->tau_cap, ntau)) || (rc = grow(p->sums, p->sums_cap, nsum))) return rc;
     bool real_tau = true;
     for (size_t i = 0; i < ntau; ++i) real_tau = real_tau && tau[2 * i + 1] == 0.0;
     // real cubes with real thresholds stay real through the whole loop (what PyWavelets does for real input)
     const bool real_path = real_dtype(dtype) && real_tau;
-    std::vector<int> done_h(nslices, 0);
-    if (active) for (int s = 0; s < nslices; ++s) done_h[s] = active[s] ? 0 : -1;
+    LoopFrame frame(p, active, nslices, niter);
     const size_t cube_bytes = elem_bytes(dtype) * p->per() * nslices;
-    if (on_plan_device(p, x)) {
-        p->cur_x = x;
-    } else {
-        P3D_TRY(hipMemcpyAsync(p->st_x, x, cube_bytes, hipMemcpyDefault, p->stream));
-        p->cur_x = p->st_x;
-    }
-    // (the loop reads the observed cube in every iteration: a result buffer that overlaps it goes through the staging buffer)
-    const char* const xb = static_cast<const char*>(x);
-    char* const ob = static_cast<char*>(out);
-    const bool direct_out = on_plan_device(p, out) && (ob + cube_bytes <= xb || xb + cube_bytes <= ob);
-    p->cur_out = direct_out ? out : p->st_out;
+    if ((rc = take_x(p, x, cube_bytes))) return rc;
+    const bool direct_out = choose_out(p, x, out, cube_bytes);
     // every copy goes onto the plan's (non-blocking) stream: a device-to-device hipMemcpy on the null stream need not have finished when it returns
     P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * p->per(), hipMemcpyDefault, p->stream));
     P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemcpyAsync(p->done, done_h.data(), sizeof(int) * nslices, hipMemcpyHostToDevice, p->stream));
-    P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nsum, p->stream));
-    P3D_TRY(hipEventRecord(p->ev0, p->stream));
+    if ((rc = frame.begin())) return rc;
     if ((rc = real_path ? w_loop<double>(p, dtype, nslices, prm) : w_loop<c64>(p, dtype, nslices, prm))) return rc;
-    P3D_TRY(hipEventRecord(p->ev1, p->stream));
-    P3D_TRY(hipMemcpyAsync(done_h.data(), p->done, sizeof(int) * nslices, hipMemcpyDeviceToHost, p->stream));
-    if (sums) P3D_TRY(hipMemcpyAsync(sums, p->sums, sizeof(double) * nsum, hipMemcpyDeviceToHost, p->stream));
-    P3D_TRY(hipStreamSynchronize(p->stream));
+    if ((rc = frame.enqueue_end(sums)) || (rc = frame.collect(niter_done, elapsed_ms))) return rc;
     if (!direct_out) {
         P3D_TRY(hipMemcpyAsync(out, p->st_out, cube_bytes, hipMemcpyDefault, p->stream));
         P3D_TRY(hipStreamSynchronize(p->stream));
-    }
-    if (niter_done) for (int s = 0; s < nslices; ++s) niter_done[s] = done_h[s] < 0 ? 0 : (done_h[s] > 0 ? done_h[s] : niter);
-    if (elapsed_ms) {
-        float ms = 0.f;
-        P3D_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-        *elapsed_ms = ms;
     }
     return P3D_OK;
 }

@@ -204,7 +204,9 @@ def test_fft_engine_host_emulation(tmp_path):
 
 def test_shared_host_helpers(tmp_path):
     """csrc/p3d_host.hpp on the CPU (tests/csrc/test_host_helpers.cpp): p3d::fail returns its code, formats its arguments and cuts a 2000-character
-    message to 511 characters; P3D_TRY leaves with P3D_ERR_HIP and '<expression> failed: <runtime's text>'; an empty DevBuf never calls hipFree."""
+    message to 511 characters; P3D_TRY leaves with P3D_ERR_HIP and '<expression> failed: <runtime's text>'; an empty DevBuf never calls hipFree;
+    and the host half of the POCS loops' frame: p3d::grow against a fake hipMalloc / hipFree, `active` -> per-slice state -> iteration counts,
+    np.percentile's ranks against hand-computed literals."""
     exe = tmp_path / "host_helpers"
     subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-I", CSRC,
                     "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "csrc", "test_host_helpers.cpp"), "-o", str(exe)], check=True)
