@@ -601,6 +601,30 @@ int p3d_segy_encode(int device, const float* section, int ntr, int ns, int layou
 int p3d_segy_decode_dev(int device, const unsigned char* records_dev, int ntr, int ns, int fmt, const int* fields, int nf, float* samples_dev, int* words_dev);
 int p3d_segy_decode(int device, const unsigned char* records, int ntr, int ns, int fmt, const int* fields, int nf, float* samples, int* words);
 
+/* ---- step 1: merging short SEG-Y files with their neighbours (p3d_merge.hip; the reference's merge_segys.py, which uses pandas and segyio) ----
+ * A record is a 240-byte trace header followed by the samples, reclen = 240 ... 240 + 4 * 65535 bytes in all, of any sample format: samples are
+ * moved as bytes.  The records of a group of files lie back to back.
+ *   keys:    per record TRACE_SEQUENCE_LINE (bytes 1-4, int32) and two 64-bit fingerprints of its header: of all 240 bytes (fp_full) and of all
+ *            but bytes 5-8, TRACE_SEQUENCE_FILE (fp_sub).  Equal headers give equal fingerprints; the converse is the caller's to confirm.
+ *            Dword l = 0 ... 59 of the header, read as a little-endian d, contributes splitmix64((l + 1) << 32 | d); the terms are XORed.
+ *   records: nout output records from a plan of three int tables [nout].  src[r] >= 0: record src[r], verbatim but for bytes 5-8 = r + 1
+ *            (big-endian).  src[r] = -1: a gap between the rows lo_row[r] < r < hi_row[r], which hold records: each of the 91 header words (SEG-Y
+ *            rev 1, 2 or 4 bytes, signed) is  (int32)(slope * (r - lo) + v_lo), slope = (v_hi - v_lo) / (hi - lo)  in IEEE double without fused
+ *            multiply-add (pandas' linear interpolation cast to int32), stored with its width; bytes 5-8 = r + 1; the samples are zero bytes.
+ *            lo_row / hi_row are read for gap rows only.
+ * P3D_ERR_INVALID before anything is launched and before any memory is touched: reclen out of range, nsrc < 1 or nout < 1, src[r] outside
+ * -1 ... nsrc - 1, a gap in the first or the last row, a gap whose lo_row / hi_row do not enclose it inside 0 ... nout - 1 or are gaps themselves,
+ * output records that overlap the input.  keys with n = 0: nothing is done.
+ * Entries with the _dev suffix: the records and the results DEVICE (any alignment of the records; 16-byte stores when reclen and both record
+ * buffers are multiples of 16, 4-byte stores for multiples of 4, single bytes otherwise); the plan is a HOST table in both forms.  Entries
+ * without the suffix: everything HOST. */
+int p3d_merge_keys_dev(int device, const unsigned char* records_dev, int n, int reclen, int* tracl_dev, uint64_t* fp_full_dev, uint64_t* fp_sub_dev);
+int p3d_merge_keys(int device, const unsigned char* records, int n, int reclen, int* tracl, uint64_t* fp_full, uint64_t* fp_sub);
+int p3d_merge_records_dev(int device, const unsigned char* records_dev, int nsrc, int reclen, int nout, const int* src, const int* lo_row, const int* hi_row,
+                          unsigned char* out_dev);
+int p3d_merge_records(int device, const unsigned char* records, int nsrc, int reclen, int nout, const int* src, const int* lo_row, const int* hi_row,
+                      unsigned char* out);
+
 #ifdef __cplusplus
 }
 #endif

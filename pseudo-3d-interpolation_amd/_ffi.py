@@ -154,6 +154,10 @@ PROTOTYPES = {
     "p3d_segy_encode": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "p3d_segy_decode_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "p3d_segy_decode": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_merge_keys_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3d_merge_keys": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3d_merge_records_dev": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "p3d_merge_records": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "p3d_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int)]),
     "p3d_wavelet_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -1343,6 +1347,51 @@ def segy_decode(records, ns, fmt, fields, device=0):
     samples, words = np.empty((ntr, max(ns, 0)), np.float32), np.empty((nf, ntr), np.int32)
     check(lib().p3d_segy_decode(int(device), _ptr(records), ntr, ns, fmt, _ptr(fields), nf, _ptr(samples), _ptr(words)))
     return samples, words
+
+
+# ---- step 1: merging SEG-Y records (include/p3d.h, p3d_merge.hip) ---------------------------------------------------
+def _merge_plan(src, lo_row, hi_row):
+    """The three HOST tables of a merge plan as int32 [nout]."""
+    src, lo_row, hi_row = (np.ascontiguousarray(t, dtype=np.int32).ravel() for t in (src, lo_row, hi_row))
+    if not src.size == lo_row.size == hi_row.size:
+        raise ValueError(f"plan tables of {src.size}, {lo_row.size} and {hi_row.size} rows")
+    return src, lo_row, hi_row
+
+
+def merge_keys_dev(records, n, reclen, tracl, fp_full, fp_sub, device=0):
+    """p3d_merge_keys_dev on device pointers: ``records`` n x reclen bytes, ``tracl`` int32 [n], ``fp_full`` / ``fp_sub`` uint64 [n]."""
+    check(lib().p3d_merge_keys_dev(int(device), records, int(n), int(reclen), tracl, fp_full, fp_sub))
+
+
+def merge_keys(records, device=0):
+    """``(tracl int32 [n], fp_full uint64 [n], fp_sub uint64 [n])`` of host records uint8 [n][reclen]: TRACE_SEQUENCE_LINE and the fingerprints of
+    the 240 header bytes with and without bytes 5-8 (p3d_merge_keys)."""
+    records = np.ascontiguousarray(records, dtype=np.uint8)
+    if records.ndim != 2:
+        raise ValueError("records are [nrecords][reclen] bytes")
+    n, reclen = records.shape
+    tracl, fp_full, fp_sub = np.empty(n, np.int32), np.empty(n, np.uint64), np.empty(n, np.uint64)
+    check(lib().p3d_merge_keys(int(device), _ptr(records), n, reclen, _ptr(tracl), _ptr(fp_full), _ptr(fp_sub)))
+    return tracl, fp_full, fp_sub
+
+
+def merge_records_dev(records, nsrc, reclen, src, lo_row, hi_row, out, device=0):
+    """p3d_merge_records_dev: ``records`` (nsrc x reclen bytes) and ``out`` (len(src) x reclen bytes) are device pointers, the plan ``src``,
+    ``lo_row``, ``hi_row`` are HOST tables."""
+    src, lo_row, hi_row = _merge_plan(src, lo_row, hi_row)
+    check(lib().p3d_merge_records_dev(int(device), records, int(nsrc), int(reclen), src.size, _ptr(src), _ptr(lo_row), _ptr(hi_row), out))
+
+
+def merge_records(records, src, lo_row, hi_row, device=0):
+    """Output records uint8 [len(src)][reclen] of host records uint8 [nsrc][reclen]: row r is record ``src[r]`` with TRACE_SEQUENCE_FILE = r + 1,
+    or for ``src[r]`` = -1 a gap trace whose header words are interpolated between rows ``lo_row[r]`` and ``hi_row[r]`` (p3d_merge_records)."""
+    records = np.ascontiguousarray(records, dtype=np.uint8)
+    if records.ndim != 2:
+        raise ValueError("records are [nrecords][reclen] bytes")
+    src, lo_row, hi_row = _merge_plan(src, lo_row, hi_row)
+    out = np.empty((src.size, records.shape[1]), np.uint8)
+    check(lib().p3d_merge_records(int(device), _ptr(records), records.shape[0], records.shape[1], src.size, _ptr(src), _ptr(lo_row), _ptr(hi_row), _ptr(out)))
+    return out
 
 
 # ---- step 2: reprojection of header coordinates (include/p3d.h, p3d_proj.hip) --------------------------------------

@@ -137,7 +137,8 @@ class SegyFile:
         nbytes = np.memmap(path, np.uint8, 'r').size - start
         if nbytes < 0 or nbytes % self._dtype.itemsize:
             raise ValueError(f'{path}: {nbytes} trace bytes are not a whole number of {self._dtype.itemsize}-byte traces')
-        self.ntraces = nbytes // self._dtype.itemsize
+        self.reclen = self._dtype.itemsize                       # bytes of one trace record, header included
+        self.ntraces = nbytes // self.reclen
         self._mm = np.memmap(path, self._dtype, 'r', offset=start, shape=(self.ntraces,))
 
     @property
