@@ -187,6 +187,29 @@ int p3d_multi_run(int ndev, const int* devices, int nil, int nxl, const void* x_
                   const double* tau, const uint8_t* active, const p3d_pocs_params* params, void* out_host, int nslices,
                   int32_t* niter_done, double* sums);
 
+/* ---- transform_kind = 'DCT': the loop with scipy.fft.dctn / idctn (type 2) as the sparsifying transform -------------------------
+ * norm: the `norm` keyword of both callables.  The DCT is computed from the plan's own batched 2-D FFT of the even/odd-reordered slice
+ * plus one pass over groups of four coefficients (csrc/p3d_dct.hip), float32 arithmetic; every shape of p3d_shape_supported is covered.
+ * Real cubes run as complex with zero imaginary part. */
+#define P3D_DCT_BACKWARD 0 /* norm=None / 'backward': unnormalised forward, 1/(2 nil * 2 nxl) inverse */
+#define P3D_DCT_ORTHO 1    /* norm='ortho' */
+/* Batched 2-D DCT-II (inverse = 0) / its inverse (inverse = 1) of complex64 slices; test hook like p3d_fft2_c64.  in == out is allowed. */
+int p3d_dct2_c64_dev(p3d_plan* plan, const void* in_dev, void* out_dev, int nslices, int inverse, int norm);
+int p3d_dct2_c64(p3d_plan* plan, const void* in_host, void* out_host, int nslices, int inverse, int norm);
+/* threshold(dctn(x), tau_s, kind) of every slice, arguments as p3d_fft2_shrink_c64: the keep/zero decision of every coefficient */
+int p3d_dct_shrink_c64(p3d_plan* plan, const void* in_host, const double* tau, int thresh_op, void* out_host, int nslices, int norm);
+/* the statistics of p3d_pocs_stats* taken from X0 = dctn(x) */
+int p3d_pocs_dct_stats_dev(p3d_plan* plan, const void* x_dev, int dtype, int nslices, double* stats_host, int norm);
+int p3d_pocs_dct_stats(p3d_plan* plan, const void* x_host, int dtype, int nslices, double* stats_host, int norm);
+/* p3d_pocs_run* with the DCT pair in place of fft2 / ifft2; every operator, version and option of p3d_pocs_params, P3D_OP_PERCENTILE
+ * included (P3D_FLAG_PRIMED and P3D_FLAG_PROFILE are ignored) */
+int p3d_pocs_dct_run_dev(p3d_plan* plan, const void* x_dev, int dtype, const float* mask_dev, const double* tau, const uint8_t* active,
+                         const p3d_pocs_params* params, void* out_dev, int nslices, int32_t* niter_done, double* sums,
+                         double* elapsed_ms, int norm);
+int p3d_pocs_dct_run(p3d_plan* plan, const void* x_host, int dtype, const float* mask_host, const double* tau, const uint8_t* active,
+                     const p3d_pocs_params* params, void* out_host, int nslices, int32_t* niter_done, double* sums,
+                     double* elapsed_ms, int norm);
+
 /* The same loop in the REFERENCE's precision.  POCS_algorithm computes in complex128 / float64 whenever its input is, under NumPy < 2 for every
  * input, and under NumPy >= 2 for the soft / garrote operators, FPOCS and APOCS on complex64 / float32 input as well (threshold_operator.py:37-39,
  * 76-78; POCS.py:566-575, 616: tau, the momentum scalar and the weights 1 - alpha * mask are float64 / complex128).  A plan64 runs

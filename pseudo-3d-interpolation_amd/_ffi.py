@@ -21,6 +21,7 @@ P3D_VER = {"regular": 0, "fast": 1, "adaptive": 2}
 P3D_FLAG_PROFILE = 1
 P3D_FLAG_PRIMED = 2
 STATS_PER_SLICE = 6
+P3D_DCT_NORM = {None: 0, "backward": 0, "ortho": 1}   # P3D_DCT_BACKWARD / P3D_DCT_ORTHO: the `norm` of scipy.fft.dctn / idctn
 
 
 class P3DError(RuntimeError):
@@ -80,6 +81,17 @@ PROTOTYPES = {
     "p3d_pocs_run_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.POINTER(PocsParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                    C.POINTER(C.c_double)]),
+    "p3d_dct2_c64_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "p3d_dct2_c64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "p3d_dct_shrink_c64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "p3d_pocs_dct_stats_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "p3d_pocs_dct_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "p3d_pocs_dct_run_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(PocsParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_double), C.c_int]),
+    "p3d_pocs_dct_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(PocsParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_double), C.c_int]),
     "p3d_pocs_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(PocsParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                C.POINTER(C.c_double)]),
@@ -395,8 +407,9 @@ class _PlanBase:
         return xc, dt, m, np.empty_like(xc)
 
     def _run_entry(self, entry, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op, version, eps, alpha, active, profile=False, want_sums=True,
-                   primed=False):
-        """One call of a p3d_*_run entry on raw pointers.  Returns (niter_done, sums or None, device ms of the loop)."""
+                   primed=False, extra=()):
+        """One call of a p3d_*_run entry on raw pointers (``extra``: what the entry takes behind the common arguments).  Returns (niter_done, sums or
+        None, device ms of the loop)."""
         t = _tau_table(tau, (n, niter) + self._tau_shape())
         act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
         prm = Plan._params(niter, thresh_op, version, eps, alpha, profile, primed)
@@ -404,7 +417,7 @@ class _PlanBase:
         sums = np.zeros((niter + 1, n), np.float64) if want_sums else None
         ms = C.c_double(0.0)
         check(getattr(lib(), entry)(self.handle, x_ptr, dtype, mask_ptr, _ptr(t), None if act is None else _ptr(act), C.byref(prm), out_ptr, n,
-                                    _ptr(done), None if sums is None else _ptr(sums), C.byref(ms)))
+                                    _ptr(done), None if sums is None else _ptr(sums), C.byref(ms), *extra))
         return done, sums, ms.value
 
     def stats(self, x):
@@ -699,6 +712,57 @@ class Plan(_PlanBase):
         """Device pointers in/out (cube stays resident in HBM).  Returns (niter_done, sums -- None unless ``want_sums`` --, elapsed_ms)."""
         return self._run_entry("p3d_pocs_run_dev", x_ptr, dtype, mask_ptr, tau, niter, out_ptr, nslices, thresh_op, version, eps, alpha, active, profile,
                                want_sums, primed)
+
+    # ---- transform_kind = 'DCT': scipy.fft.dctn / idctn (type 2) as the transform of the loop ------------
+    @staticmethod
+    def _dct_norm(norm):
+        if norm not in P3D_DCT_NORM:
+            raise UnsupportedError(P3D_ERR_UNSUPPORTED, f"DCT norm {norm!r} is not implemented by the HIP kernels (None, 'backward', 'ortho')")
+        return P3D_DCT_NORM[norm]
+
+    def dct2(self, x, inverse=False, norm=None):
+        """scipy.fft.dctn (``inverse``: idctn) of complex64 slices over the last two axes, type 2."""
+        x = np.asarray(x)
+        squeeze = x.ndim == 2
+        xc, _ = self._cube(x.astype(np.complex64, copy=False))
+        out = np.empty_like(xc)
+        check(lib().p3d_dct2_c64(self.handle, _ptr(xc), _ptr(out), xc.shape[0], int(bool(inverse)), self._dct_norm(norm)))
+        return out[0] if squeeze else out
+
+    def dct_shrink(self, x, tau, thresh_op="hard", norm=None):
+        """threshold(dctn(x), tau, kind) on the device; ``tau`` scalar or one value per slice."""
+        x = np.asarray(x)
+        squeeze = x.ndim == 2
+        xc, _ = self._cube(x.astype(np.complex64, copy=False))
+        n = xc.shape[0]
+        t = _tau_table(tau, (n,))
+        out = np.empty_like(xc)
+        check(lib().p3d_dct_shrink_c64(self.handle, _ptr(xc), _ptr(t), P3D_OP[thresh_op], _ptr(out), n, self._dct_norm(norm)))
+        return out[0] if squeeze else out
+
+    def dct_stats(self, x, norm=None):
+        xc, dt = self._cube(x)
+        st = np.empty((xc.shape[0], STATS_PER_SLICE), np.float64)
+        check(lib().p3d_pocs_dct_stats(self.handle, _ptr(xc), dt, xc.shape[0], _ptr(st), self._dct_norm(norm)))
+        return st
+
+    def dct_stats_dev(self, x_ptr, dtype, nslices, norm=None):
+        st = np.empty((nslices, STATS_PER_SLICE), np.float64)
+        check(lib().p3d_pocs_dct_stats_dev(self.handle, x_ptr, dtype, nslices, _ptr(st), self._dct_norm(norm)))
+        return st
+
+    def dct_run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None, norm=None):
+        """`run` with the DCT pair as the transform.  Returns (out, niter_done, sums, elapsed_ms)."""
+        xc, dt, m, out = self._host_job(x, mask)
+        done, sums, ms = self._run_entry("p3d_pocs_dct_run", _ptr(xc), dt, _ptr(m), tau, niter, _ptr(out), xc.shape[0], thresh_op, version, eps, alpha,
+                                         active, extra=(self._dct_norm(norm),))
+        return out, done, sums, ms
+
+    def dct_run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, nslices, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None,
+                    norm=None, want_sums=True):
+        """`run_dev` with the DCT pair as the transform.  Returns (niter_done, sums, elapsed_ms)."""
+        return self._run_entry("p3d_pocs_dct_run_dev", x_ptr, dtype, mask_ptr, tau, niter, out_ptr, nslices, thresh_op, version, eps, alpha, active,
+                               want_sums=want_sums, extra=(self._dct_norm(norm),))
 
     def last_sparsity(self):
         """Fraction of 8-column spectrum blocks that kept a coefficient in the last run (-1: dense path)."""

@@ -12,6 +12,8 @@
 #include <vector>
 
 #include "p3d.h"
+#include "p3d_dct.hpp"
+#include "p3d_dct_tables.hpp"
 #include "p3d_generic.hpp"
 #include "p3d_host.hpp"
 #include "p3d_internal.hpp"
@@ -374,6 +376,9 @@ struct p3d_plan {
     } primed;
     double* sum0 = nullptr;     // [max_slices] sum |x_obs| of the primed cube
     int sorted_slices = 0;      // p3d_pocs_sorted_spectrum: st_x holds the sorted order keys of that many slices (0: none)
+    // transform_kind = 'DCT' (p3d_dct.hip), allocated by the first DCT call on the plan:
+    c32* dct_w = nullptr;       // tuned plans: the row-major iterate [max_slices][nil][nxl] (a generic plan's work buffer is row-major itself)
+    c32* dct_tab = nullptr;     // [2 norms][fwd nil | inv nil | fwd nxl | inv nxl] (p3d_dct_tables.hpp)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> prof_events;
     double prof_col_ms = 0, prof_row_ms = 0;
@@ -435,7 +440,7 @@ int p3d_plan_destroy(p3d_plan* p)
     if (p->pct_plan) p3d_plan_destroy(p->pct_plan);
     hipSetDevice(p->device);
     if (p->stream) hipStreamSynchronize(p->stream);
-    void* bufs[] = {p->mbits, p->mbase, p->cbase, p->bits64, p->bits32, p->tw32, p->nzl, p->nzflag, p->nzm, p->nzcount, p->tw_col, p->tw_row, p->work, p->bits, p->flag, p->rowbase, p->xc, p->sums, p->rowsum, p->sum0, p->tau, p->pct_sel, p->pct_hist, p->pct_frac,
+    void* bufs[] = {p->mbits, p->mbase, p->cbase, p->bits64, p->bits32, p->tw32, p->nzl, p->nzflag, p->nzm, p->nzcount, p->tw_col, p->tw_row, p->work, p->bits, p->flag, p->rowbase, p->xc, p->sums, p->rowsum, p->sum0, p->tau, p->pct_sel, p->pct_hist, p->pct_frac, p->dct_w, p->dct_tab,
                     p->done,   p->partials, p->st_x, p->st_out, p->st_mask};
     for (void* b : bufs)
         if (b) hipFree(b);
@@ -1724,6 +1729,223 @@ int p3d_pocs_run(p3d_plan* p, const void* x, int dtype, const float* mask, const
     if ((rc = p3d_pocs_run_dev(p, p->st_x, dtype, p->st_mask, tau, active, prm, p->st_out, nslices, niter_done, sums,
                                elapsed_ms)))
         return rc;
+    P3D_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
+    return P3D_OK;
+}
+
+// ---- transform_kind = 'DCT' (p3d_dct.hip): dctn / idctn of type 2 from the plan's own 2-D FFT --------------------------------------------
+// the iterate buffer, the coefficient tables of both norms and the percentile state, allocated on the first DCT call of a plan
+static int dct_ensure(p3d_plan* p)
+{
+    const size_t ms = (size_t)p->max_slices;
+    if (!p->generic && !p->dct_w) {
+        const size_t n = p->slice_elems() * ms;
+        P3D_TRY(hipMalloc((void**)&p->dct_w, sizeof(c32) * n));
+        P3D_TRY(hipMemsetAsync(p->dct_w, 0, sizeof(c32) * n, p->stream));   // (slices a job switches off are transformed all the same: keep them finite)
+    }
+    if (!p->dct_tab) {
+        const size_t per = 2 * ((size_t)p->nil + p->nxl);
+        std::vector<c32> host(2 * per);
+        for (int norm = 0; norm < 2; ++norm) {
+            c32* b = host.data() + norm * per;
+            dct::build_tables(p->nil, norm, b, b + p->nil);
+            dct::build_tables(p->nxl, norm, b + 2 * (size_t)p->nil, b + 2 * (size_t)p->nil + p->nxl);
+        }
+        P3D_TRY(hipMalloc((void**)&p->dct_tab, sizeof(c32) * host.size()));
+        P3D_TRY(hipMemcpy(p->dct_tab, host.data(), sizeof(c32) * host.size(), hipMemcpyHostToDevice));
+    }
+    if (!p->pct_sel) P3D_TRY(hipMalloc((void**)&p->pct_sel, sizeof(unsigned) * 16 * ms));
+    if (!p->pct_hist) P3D_TRY(hipMalloc((void**)&p->pct_hist, sizeof(unsigned) * 2048 * ms));
+    if (!p->pct_frac) P3D_TRY(hipMalloc((void**)&p->pct_frac, sizeof(float) * ms));
+    return P3D_OK;
+}
+static c32* dct_buf(p3d_plan* p) { return p->generic ? p->work : p->dct_w; }
+static DctTab dct_tab(p3d_plan* p, int norm)
+{
+    const c32* b = p->dct_tab + (size_t)norm * 2 * ((size_t)p->nil + p->nxl);
+    return DctTab{b, b + p->nil, b + 2 * (size_t)p->nil, b + 2 * (size_t)p->nil + p->nxl};
+}
+static int dct_check(p3d_plan* p, int nslices, int norm)
+{
+    int rc = check_batch(p, nslices);
+    if (rc) return rc;
+    if (norm != P3D_DCT_BACKWARD && norm != P3D_DCT_ORTHO) return fail(P3D_ERR_UNSUPPORTED, "DCT norm %d is not implemented (backward, ortho)", norm);
+    P3D_TRY(hipSetDevice(p->device));
+    return dct_ensure(p);
+}
+// x (device, complex64 or float32) -> reordered iterate -> fft2 -> combine: the plan's DCT buffer holds X = dctn(x); sum |x| per slice goes to `sums`
+static int dct_forward(p3d_plan* p, const void* x, int dtype, int nslices, int norm, double* sums)
+{
+    c32* const W = dct_buf(p);
+    P3D_TRY(dct_launch_update(W, x, dtype, nullptr, nullptr, sums, 0, 0, 0, 1.0f, nslices, p->nil, p->nxl, nullptr, 0, p->stream));
+    if (int rc = fft2_enqueue(p, W, W, nslices, 0)) return rc;
+    P3D_TRY(dct_launch_group(DCT_COMBINE, W, dct_tab(p, norm), nullptr, 1, 0, 0, nslices, p->nil, p->nxl, nullptr, p->stream));
+    return P3D_OK;
+}
+
+int p3d_dct2_c64_dev(p3d_plan* p, const void* in, void* out, int nslices, int inverse, int norm)
+{
+    int rc = dct_check(p, nslices, norm);
+    if (rc) return rc;
+    if (!in || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
+    c32* const W = dct_buf(p);
+    const size_t bytes = sizeof(c32) * p->slice_elems() * nslices;
+    if (!inverse) {
+        P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * nslices, p->stream));
+        if ((rc = dct_forward(p, in, P3D_C64, nslices, norm, p->rowsum))) return rc;
+        P3D_TRY(hipMemcpyAsync(out, W, bytes, hipMemcpyDeviceToDevice, p->stream));
+    } else {
+        P3D_TRY(hipMemcpyAsync(W, in, bytes, hipMemcpyDeviceToDevice, p->stream));
+        P3D_TRY(dct_launch_group(DCT_SPLIT, W, dct_tab(p, norm), nullptr, 1, 0, 0, nslices, p->nil, p->nxl, nullptr, p->stream));
+        if ((rc = fft2_enqueue(p, W, W, nslices, 1))) return rc;
+        P3D_TRY(dct_launch_update(W, nullptr, P3D_C64, nullptr, out, nullptr, 2, 0, 0, 1.0f, nslices, p->nil, p->nxl, nullptr, 0, p->stream));
+    }
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    return P3D_OK;
+}
+
+int p3d_dct2_c64(p3d_plan* p, const void* in, void* out, int nslices, int inverse, int norm)
+{
+    int rc = dct_check(p, nslices, norm);
+    if (rc) return rc;
+    if (!in || !out) return fail(P3D_ERR_INVALID, "NULL buffer");
+    const size_t bytes = sizeof(c32) * p->slice_elems() * nslices;
+    if ((rc = ensure_staging(p, sizeof(c32) * p->slice_elems() * p->max_slices))) return rc;
+    P3D_TRY(hipMemcpy(p->st_x, in, bytes, hipMemcpyHostToDevice));
+    if ((rc = p3d_dct2_c64_dev(p, p->st_x, p->st_out, nslices, inverse, norm))) return rc;
+    P3D_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
+    return P3D_OK;
+}
+
+int p3d_dct_shrink_c64(p3d_plan* p, const void* in, const double* tau, int op, void* out, int nslices, int norm)
+{
+    int rc = dct_check(p, nslices, norm);
+    if (rc) return rc;
+    if (!in || !out || !tau) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (op < P3D_OP_HARD || op > P3D_OP_GARROTE) return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented", op);
+    const size_t bytes = sizeof(c32) * p->slice_elems() * nslices;
+    if ((rc = ensure_staging(p, sizeof(c32) * p->slice_elems() * p->max_slices))) return rc;
+    if ((rc = grow(p->tau, p->tau_cap, (size_t)nslices))) return rc;
+    std::vector<c32> tau_f(nslices);
+    for (int s = 0; s < nslices; ++s) tau_f[s] = tau_for_device(tau[2 * s], tau[2 * s + 1], op == P3D_OP_HARD);
+    P3D_TRY(hipMemcpy(p->tau, tau_f.data(), sizeof(c32) * nslices, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(p->st_x, in, bytes, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * nslices, p->stream));
+    if ((rc = dct_forward(p, p->st_x, P3D_C64, nslices, norm, p->rowsum))) return rc;
+    P3D_TRY(gen_launch_shrink(dct_buf(p), p->tau, 1, 0, op, nslices, p->slice_elems(), nullptr, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    P3D_TRY(hipMemcpy(out, dct_buf(p), bytes, hipMemcpyDeviceToHost));
+    return P3D_OK;
+}
+
+int p3d_pocs_dct_stats_dev(p3d_plan* p, const void* x, int dtype, int nslices, double* stats, int norm)
+{
+    int rc = dct_check(p, nslices, norm);
+    if (rc) return rc;
+    if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * nslices, p->stream));
+    if ((rc = dct_forward(p, x, dtype, nslices, norm, p->rowsum))) return rc;
+    const int blocks = std::min(p->tiles, (int)p3d_plan::GEN_STAT_BLOCKS);   // (the partials buffer holds at least `tiles` records per slice)
+    P3D_TRY(gen_launch_stats(dct_buf(p), p->partials, nslices, p->slice_elems(), blocks, p->stream));
+    return reduce_partials(p, nslices, stats, blocks);
+}
+
+int p3d_pocs_dct_stats(p3d_plan* p, const void* x, int dtype, int nslices, double* stats, int norm)
+{
+    int rc = dct_check(p, nslices, norm);
+    if (rc) return rc;
+    if (!x || !stats) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    if ((rc = ensure_staging(p, sizeof(c32) * p->slice_elems() * p->max_slices))) return rc;
+    const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
+    P3D_TRY(hipMemcpy(p->st_x, x, esz * p->slice_elems() * nslices, hipMemcpyHostToDevice));
+    return p3d_pocs_dct_stats_dev(p, p->st_x, dtype, nslices, stats, norm);
+}
+
+// run_generic with the DCT in place of the FFT: first input, then per iteration fft2 -> group pass (combine, threshold, split) -> ifft2 -> re-insertion;
+// the percentile operators split the group pass around the ranking of |X|
+int p3d_pocs_dct_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, const double* tau, const uint8_t* active, const p3d_pocs_params* prm,
+                         void* out, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms, int norm)
+{
+    int rc = dct_check(p, nslices, norm);
+    if (rc) return rc;
+    if (!x || !mask || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
+    const bool percentile = (prm->thresh_op & P3D_OP_PERCENTILE) != 0;
+    const int base_op = prm->thresh_op & ~P3D_OP_PERCENTILE;
+    if (base_op < P3D_OP_HARD || base_op > P3D_OP_GARROTE)
+        return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d is not implemented by the HIP kernels", prm->thresh_op);
+    if (prm->version < P3D_VER_REGULAR || prm->version > P3D_VER_ADAPTIVE) return fail(P3D_ERR_INVALID, "unknown version %d", prm->version);
+
+    const int niter = prm->niter, n1 = p->nil, n2 = p->nxl;
+    const size_t ntau = (size_t)nslices * niter, per_slice = p->slice_elems();
+    if ((rc = grow(p->tau, p->tau_cap, ntau)) || (rc = grow(p->sums, p->sums_cap, (size_t)(niter + 1) * nslices))) return rc;
+    std::vector<c32> tau_f(ntau);
+    for (size_t i = 0; i < ntau; ++i) tau_f[i] = tau_for_device(tau[2 * i], tau[2 * i + 1], prm->thresh_op == P3D_OP_HARD);
+    LoopFrame frame(p, active, nslices, niter);
+    P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
+    if ((rc = frame.begin())) return rc;
+
+    const bool early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE;
+    const int* done_d = (early || frame.any_off()) ? p->done : nullptr;
+    c32* const W = dct_buf(p);
+    const DctTab tab = dct_tab(p, norm);
+    const float alpha = (float)prm->alpha;
+    P3D_TRY(dct_launch_update(W, x, dtype, mask, out, p->sums, 0, adaptive ? 1 : 0, 0, alpha, nslices, n1, n2, done_d, 0, p->stream));
+    std::vector<unsigned> sel_h;
+    std::vector<float> frac_h;
+    for (int k = 0; k < niter; ++k) {
+        const bool last = k + 1 == niter;
+        if ((rc = fft2_enqueue(p, W, W, nslices, 0))) return rc;
+        if (percentile) {  // tau[s][k] <- np.percentile(|X_s|, perc_k) of the DCT spectrum: the group pass in two halves around the ranking
+            P3D_TRY(dct_launch_group(DCT_COMBINE, W, tab, p->tau, niter, k, base_op, nslices, n1, n2, done_d, p->stream));
+            sel_h.assign((size_t)nslices * 16, 0u);
+            frac_h.assign(nslices, 0.f);
+            for (int s = 0; s < nslices; ++s)
+                percentile_rank(tau[2 * ((size_t)s * niter + k)], per_slice, &sel_h[(size_t)s * 8], &sel_h[((size_t)nslices + s) * 8], &frac_h[s]);
+            P3D_TRY(hipMemcpyAsync(p->pct_sel, sel_h.data(), sizeof(unsigned) * sel_h.size(), hipMemcpyHostToDevice, p->stream));
+            P3D_TRY(hipMemcpyAsync(p->pct_frac, frac_h.data(), sizeof(float) * nslices, hipMemcpyHostToDevice, p->stream));
+            P3D_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * 2048 * (size_t)nslices, p->stream));
+            for (int which = 0; which < 2; ++which) {
+                unsigned* sel = p->pct_sel + (size_t)which * nslices * 8;
+                for (int level = 0; level < 3; ++level) {
+                    P3D_TRY(gen_launch_pct_hist(W, per_slice, sel, p->pct_hist, level, nslices, p->stream));
+                    P3D_TRY(gen_launch_pct_scan(sel, p->pct_hist, level, nslices, p->stream));
+                }
+            }
+            P3D_TRY(gen_launch_pct_tau(p->pct_sel, p->pct_sel + (size_t)nslices * 8, p->pct_frac, p->tau, niter, k, nslices, p->stream));
+            P3D_TRY(hipStreamSynchronize(p->stream));  // sel_h / frac_h are reused next iteration
+            P3D_TRY(dct_launch_group(DCT_SHRINK_SPLIT, W, tab, p->tau, niter, k, base_op, nslices, n1, n2, done_d, p->stream));
+        } else {
+            P3D_TRY(dct_launch_group(DCT_FUSED, W, tab, p->tau, niter, k, base_op, nslices, n1, n2, done_d, p->stream));
+        }
+        if ((rc = fft2_enqueue(p, W, W, nslices, 1))) return rc;
+        P3D_TRY(dct_launch_update(W, x, dtype, mask, out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0,
+                                  alpha, nslices, n1, n2, p->done, last ? 1 : 0, p->stream));
+        if (early) conv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
+    }
+    P3D_TRY(hipGetLastError());
+    if ((rc = frame.enqueue_end(sums)) || (rc = frame.collect(niter_done, elapsed_ms))) return rc;
+    p->last_nonzero_fraction = -1.0;
+    p->prof_col_n = p->prof_row_n = 0;
+    return P3D_OK;
+}
+
+int p3d_pocs_dct_run(p3d_plan* p, const void* x, int dtype, const float* mask, const double* tau, const uint8_t* active, const p3d_pocs_params* prm,
+                     void* out, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms, int norm)
+{
+    int rc = dct_check(p, nslices, norm);
+    if (rc) return rc;
+    if (!x || !mask || !out) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    if ((rc = ensure_staging(p, sizeof(c32) * p->slice_elems() * p->max_slices))) return rc;
+    const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
+    const size_t bytes = esz * p->slice_elems() * nslices;
+    P3D_TRY(hipMemcpy(p->st_x, x, bytes, hipMemcpyHostToDevice));
+    P3D_TRY(hipMemcpy(p->st_mask, mask, sizeof(float) * p->slice_elems(), hipMemcpyHostToDevice));
+    if ((rc = p3d_pocs_dct_run_dev(p, p->st_x, dtype, p->st_mask, tau, active, prm, p->st_out, nslices, niter_done, sums, elapsed_ms, norm))) return rc;
     P3D_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
     return P3D_OK;
 }

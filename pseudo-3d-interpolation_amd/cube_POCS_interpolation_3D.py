@@ -8,7 +8,8 @@ dask ``LocalCluster`` slice farm (:291-340) is replaced by whole batches of slic
 ``fold <= 1 ? fold : 1`` (:242-244), same output naming (:146-157, :223-228), ``.real`` / ``.imag`` split (:160-164),
 per-batch ``slice-XXXX-YYYY.out`` runtime files merged into ``runtimes_<prefix>.txt`` (:177-195), same attributes
 (:346-367).  Cubes are ``.npz`` files (cube_io.py) or netCDF when xarray is installed.  ``transform_kind``: FFT, WAVELET (with the ``wavelet`` key, default
-coif5, :261) or SHEARLET (spectra from functions/shearlets.py instead of FFST, :269-272); the other kinds raise as the reference does when their third-party package is missing (:287-288).
+coif5, :261), SHEARLET (spectra from functions/shearlets.py instead of FFST, :269-272) or DCT (not in the reference's driver: scipy.fft.dctn / idctn of type 2,
+the optional ``dct_norm`` key -- ``ortho`` when absent, or ``backward`` -- joins the output prefix like the wavelet's name); the other kinds raise as the reference does when their third-party package is missing (:287-288).
 """
 import argparse
 import datetime
@@ -76,6 +77,15 @@ def combine_runtime_results(dir_files: str, prefix: str = 'combined', fsuffix: s
                 fout.write(f.read())
 
 
+def dct_norm_from_metadata(metadata):
+    """The optional ``dct_norm`` key of the YAML ``metadata`` block for ``transform_kind: DCT``: 'ortho' (when absent) or 'backward'."""
+    norm = metadata.get('dct_norm')
+    norm = 'ortho' if norm is None else str(norm).lower()
+    if norm not in ('ortho', 'backward'):
+        raise ValueError(f"dct_norm must be 'ortho' or 'backward', got {metadata.get('dct_norm')!r}")
+    return norm
+
+
 def main(argv=sys.argv, return_dataset=False):
     """Interpolate sparse 3D cube."""
     SCRIPT = os.path.basename(__file__)
@@ -121,6 +131,10 @@ def main(argv=sys.argv, return_dataset=False):
         metadata['wavelet'] = wavelet
         metadata['transform'] = metadata['itransform'] = None
         prefix += f'_{wavelet}-{wavelet_mode}'
+    elif TRANSFORM == 'DCT':                                 # an extension over the reference's driver: scipy.fft.dctn / idctn, type 2
+        metadata['dct_norm'] = dct_norm_from_metadata(metadata)
+        metadata['transform'] = metadata['itransform'] = None
+        prefix += f"_{metadata['dct_norm']}"
     elif TRANSFORM == 'SHEARLET':                            # cube_POCS_interpolation_3D.py:269-274
         from .functions.shearlets import scalesShearsAndSpectra
         Psi = scalesShearsAndSpectra(data.shape[1:], numOfScales=None, realCoefficients=True, fftshift_spectra=True, dtype=np.float32)

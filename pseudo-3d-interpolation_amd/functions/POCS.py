@@ -10,7 +10,8 @@ keep working, plus :func:`pocs_cube`, which hands a whole batch of slices to the
 What runs where
 ---------------
 * GPU (libp3d_hip.so, hand-written HIP): the forward transform of the observed slice and its
-  statistics, and the whole iteration loop (forward FFT2, thresholding -- for the ``-percentile``
+  statistics, and the whole iteration loop (forward FFT2 -- or the wavelet, shearlet or cosine
+  transform that ``transform_kind`` names --, thresholding -- for the ``-percentile``
   operators including the exact ``np.percentile`` of the spectrum moduli --, inverse FFT2,
   re-insertion of the observed traces, cost sums, early exit).
 * Host (this file, a few scalars per slice): argument checks and the threshold schedule
@@ -29,7 +30,7 @@ from .. import _ffi
 from .shearlets import get_number_scales
 
 TRANSFORMS = ('FFT', 'WAVELET', 'SHEARLET', 'CURVELET', 'DCT')
-_HIP_TRANSFORMS = ('FFT', 'WAVELET', 'SHEARLET')
+_HIP_TRANSFORMS = ('FFT', 'WAVELET', 'SHEARLET', 'DCT')
 _WAVELET_OPS = ('soft', 'hard', 'garrote', 'garotte')
 _THRESH_OPS = ('soft', 'hard', 'garrote', 'garotte', 'soft-percentile', 'hard-percentile',
                'garrote-percentile', 'garotte-percentile')
@@ -797,6 +798,7 @@ def pocs_cube(
     auxiliary_data=None,
     precision=None,
     out=None,
+    dct_norm=None,
     **ignored,
 ):
     """
@@ -823,6 +825,10 @@ def pocs_cube(
     garrote operators, the FFT and SHEARLET ones slice extents up to 5120;
     a call that asks for (or implies) double precision outside that coverage runs the float32 kernels and says so with a ``RuntimeWarning``.
 
+    ``dct_norm`` (``transform_kind='DCT'``): the ``norm`` of the ``scipy.fft.dctn`` / ``idctn`` pair (type 2) the loop runs -- ``'backward'`` or
+    ``'ortho'``.  ``None``: the ``norm`` keyword of a ``transform`` partial handed over in ``**ignored``, else SciPy's default ``'backward'``.  The
+    float32 kernels only; ``thresh_model='data-driven'`` is not available with it.
+
     ``out`` (optional): an array of the shape and dtype of ``cube`` to write the result into (e.g. a slab of the merged cube of the
     step-13 driver) instead of a new one.
 
@@ -834,6 +840,10 @@ def pocs_cube(
         out = np.empty_like(cube)
     elif not isinstance(out, np.ndarray) or out.shape != cube.shape or out.dtype != cube.dtype:
         raise ValueError(f'out must be a NumPy array of shape {cube.shape} and dtype {cube.dtype}')
+    if kind == 'DCT':
+        dct_norm = _dct_norm(ignored.get('transform'), dct_norm)
+        if thresh_model == 'data-driven':
+            raise NotImplementedError("thresh_model='data-driven' is not implemented for the DCT transform (the sorted-spectrum entry is FFT-only)")
     if cube.shape[0] == 0:
         return out
     # Plans, chunk workers and the batch buffers are cached per device and are not re-entrant (include/p3d.h: "a plan is bound to one
@@ -841,7 +851,7 @@ def pocs_cube(
     # results as a serial one; calls on different devices run side by side.
     with _device_lock(device):
         return _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version,
-                                 results, device, batch_slices, wavelet, auxiliary_data, precision, out, ignored)
+                                 results, device, batch_slices, wavelet, auxiliary_data, precision, out, ignored, dct_norm)
 
 
 def _double_loop_wanted(dtype, nil, nxl, kind, thresh_op, precision, wavelet=None, transform=None, auxiliary_data=None):
@@ -871,7 +881,7 @@ def _double_loop_wanted(dtype, nil, nxl, kind, thresh_op, precision, wavelet=Non
 
 
 def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, results, device,
-                      batch_slices, wavelet, auxiliary_data, precision, out, ignored):
+                      batch_slices, wavelet, auxiliary_data, precision, out, ignored, dct_norm=None):
     """``pocs_cube`` behind its argument checks, with the device's lock held."""
     nslices, nil, nxl = cube.shape
     step = int(batch_slices) if batch_slices else nslices
@@ -918,6 +928,8 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
             raise IndexError('list index out of range (decay_kind="factors" yields one tau per iteration, the WAVELET '
                              'thresholding needs one per level and detail)')
         plan = _get_wavelet_plan(nil, nxl, min(step, nslices), _wavelet_name(ignored.get('transform'), wavelet), device)
+    elif kind == 'DCT':
+        plan = _get_plan(nil, nxl, min(step, nslices), device, slot=15)   # the FFT plan: the DCT runs on its transforms (batch loop at the end)
     elif thresh_model != 'data-driven' and out.flags.c_contiguous:
         # FFT, statistics-driven schedules: chunks go through device buffers, uploaded once each, two chunks in flight
         slice_bytes = nil * nxl * (8 if np.iscomplexobj(cube) else 4)
@@ -1016,8 +1028,8 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
                 f.result()
         return out
 
-    # FFT, the schedules that need the sorted spectrum (or a result array that is not contiguous): one batch at a time, resident between one
-    # upload and one download like the WAVELET / SHEARLET batches above
+    # FFT, the schedules that need the sorted spectrum (or a result array that is not contiguous), and DCT: one batch at a time, resident between
+    # one upload and one download like the WAVELET / SHEARLET batches above
     narrow = np.complex64 if np.iscomplexobj(cube) else np.float32
     xd, od, md = _batch_buffers(device, nil * nxl * np.dtype(narrow).itemsize * min(step, nslices), maskf.nbytes)
     md.upload(maskf)
@@ -1031,12 +1043,15 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
         if thresh_model == 'data-driven':
             tau = _data_driven_batch(plan, chunk, active, niter, p_max, p_min, x_dev=xd.ptr if dt == _ffi.P3D_C64 else None)
         else:
-            stats = plan.stats_dev(xd.ptr, dt, n)
+            stats = plan.dct_stats_dev(xd.ptr, dt, n, norm=dct_norm) if kind == 'DCT' else plan.stats_dev(xd.ptr, dt, n)
             stats[~active] = 1.0  # keep NaNs of empty slices out of the (unused) schedule rows
+            if kind == 'DCT' and dt == _ffi.P3D_F32:
+                stats[:, 1] = 0.0  # the DCT of a real slice is real (the complex kernels leave rounding noise in the imaginary part): a real schedule
             tau = _schedule_from_stats(stats, nil * nxl, thresh_model, niter, p_max, p_min, decay_kind)
         if sqrt_decay:
             tau = np.sqrt(tau)  # POCS.py:595
-        done, sums, _ = plan.run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active)
+        run_dev = partial(plan.dct_run_dev, norm=dct_norm) if kind == 'DCT' else plan.run_dev
+        done, sums, _ = run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active)
         dst = out[lo:lo + n]
         if dst.dtype == xc.dtype and dst.flags.c_contiguous:
             od.download_into(dst)
@@ -1066,14 +1081,51 @@ def _unwrap_partial(func):
     return func, kw
 
 
+_DCT_MODULES = ('scipy.fft', 'scipy.fftpack')
+_DCT_AXES = ((-2, -1), (0, 1))   # the last two axes of a 2-D slice, as tuples
+_DCT_NORMS = (None, 'backward', 'ortho')
+
+
+def _dct_keywords_ok(kw):
+    """Keywords of a ``dctn`` / ``idctn`` partial the kernels honour: type 2 (or absent), norm None / 'backward' / 'ortho', the last two axes."""
+    for k, v in kw.items():
+        if k == 'type':
+            if isinstance(v, bool) or v != 2:
+                return False
+        elif k == 'norm':
+            if v not in _DCT_NORMS:
+                return False
+        elif k == 'axes':
+            if not (v is None or (isinstance(v, (tuple, list)) and tuple(v) in _DCT_AXES)):
+                return False
+        else:   # s=, orthogonalize=, overwrite_x=, workers= ...: not part of what the kernels compute
+            return False
+    return True
+
+
+def _dct_norm(transform, dct_norm=None):
+    """The norm of the DCT pair: an explicit ``dct_norm`` wins over the ``norm`` keyword of the ``transform`` partial, which wins over SciPy's default."""
+    if dct_norm is None:
+        _, kw = _unwrap_partial(transform) if transform is not None else (None, None)
+        dct_norm = (kw or {}).get('norm')
+    if dct_norm is None:
+        dct_norm = 'backward'
+    if dct_norm not in ('backward', 'ortho'):
+        raise NotImplementedError(f"dct_norm={dct_norm!r}: the HIP kernels implement 'backward' and 'ortho'")
+    return dct_norm
+
+
 def _check_transform_callables(kind, transform, itransform):
     """The reference CALLS ``transform`` / ``itransform`` (POCS.py:535, 592, 613); here the HIP kernels are the transform, chosen by
     ``transform_kind``.  A callable that is not the one the kind names would be ignored silently -- refuse it instead: FFT wants
     ``fft2`` / ``ifft2`` of numpy.fft (or a drop-in: scipy.fft, pyfftw.interfaces, mkl_fft) over the last two axes, WAVELET
     ``partial(pywt.wavedec2, ...)`` / ``partial(pywt.waverec2, ...)``, SHEARLET FFST's ``shearletTransformSpect`` /
-    ``inverseShearletTransformSpect`` (cube_POCS_interpolation_3D.py:255-274)."""
-    want = {'FFT': ('fft2', 'ifft2'), 'WAVELET': ('wavedec2', 'waverec2'),
+    ``inverseShearletTransformSpect`` (cube_POCS_interpolation_3D.py:255-274), DCT ``dctn`` / ``idctn`` of scipy.fft or scipy.fftpack, bare or as
+    partials with ``type`` 2, ``norm`` None / 'backward' / 'ortho' (the same on both) and the last two axes -- recognised by name and module string,
+    SciPy need not be installed."""
+    want = {'FFT': ('fft2', 'ifft2'), 'WAVELET': ('wavedec2', 'waverec2'), 'DCT': ('dctn', 'idctn'),
             'SHEARLET': ('shearletTransformSpect', 'inverseShearletTransformSpect')}[kind]
+    norms = []
     for func, name, role in ((transform, want[0], 'transform'), (itransform, want[1], 'itransform')):
         inner, kw = _unwrap_partial(func)
         fname = getattr(inner, '__name__', type(inner).__name__)
@@ -1081,6 +1133,11 @@ def _check_transform_callables(kind, transform, itransform):
         if kind == 'FFT':
             ok = ok and fname == name and str(getattr(inner, '__module__', '')).startswith(_FFT_MODULES)
             ok = ok and all(k in _FFT_BENIGN and v in _FFT_BENIGN[k] for k, v in (kw or {}).items())
+        elif kind == 'DCT':
+            mod = str(getattr(inner, '__module__', ''))
+            ok = ok and fname == name and any(mod == m or mod.startswith(m + '.') for m in _DCT_MODULES) and _dct_keywords_ok(kw or {})
+            norms.append((kw or {}).get('norm') or 'backward')
+            ok = ok and norms[0] == norms[-1]   # (the pair must invert each other)
         else:   # third-party functions (pywt / FFST need not be installed here): recognised by name
             ok = ok and fname.endswith(name)
         if not ok:
@@ -1120,7 +1177,8 @@ def POCS_algorithm(
     part; POCS.py:653-656) follow the reference.  Differences: ``transform`` / ``itransform`` must be
     supplied and must be the functions ``transform_kind`` names (``np.fft.fft2`` / ``ifft2`` for ``'FFT'``; partials of
     ``pywt.wavedec2`` / ``waverec2`` for ``'WAVELET'``, the wavelet name read from ``transform.keywords['wavelet']`` as set up by
-    the step-13 driver; FFST's ``shearletTransformSpect`` pair for ``'SHEARLET'`` with the spectra in ``auxiliary_data``) -- they
+    the step-13 driver; FFST's ``shearletTransformSpect`` pair for ``'SHEARLET'`` with the spectra in ``auxiliary_data``; ``scipy.fft.dctn`` / ``idctn`` of type 2, bare or as
+    partials, for ``'DCT'``, their ``norm`` -- None / 'backward' or 'ortho', the same on both -- read from the keywords) -- they
     are not called, the HIP kernels are the transform, and any other callable raises ``NotImplementedError`` instead of being
     ignored; arithmetic is float32 on the GPU.
     """
