@@ -386,7 +386,10 @@ int p3d_agc_dev(int device, const float* x_dev, size_t nt, size_t ntraces, int w
  *       curves: HOST [4][nt] doubles (tpow, epow, linear, pgc factors; pgc is applied in float32), NULL when no curve is used; work:
  *       DEVICE [nt][ntraces] floats, needed with AGC, qclip or norm_rms splitting the pass (may be NULL otherwise).
  *   p3d_pre_sosfiltfilt_dev: scipy.signal.sosfiltfilt(sos, x, padtype='odd', padlen) along twt, sos / zi HOST [nsec][6] / [nsec][2]
- *       (sosfilt_zi), double-precision recursion; work: DEVICE [nt + 2 padlen][ntraces] floats or NULL (allocated).
+ *       (sosfilt_zi), double-precision recursion; work: DEVICE [nt + 2 padlen][ntraces] floats for nsec <= 8, DOUBLES (8-byte
+ *       aligned) for longer cascades, which run in groups of 8 sections with the signal between the groups held in double; or NULL
+ *       (allocated).  A misaligned work buffer is refused (P3D_ERR_INVALID), and so is one too short where the runtime can tell: the
+ *       room is counted to the end of the allocation that holds the pointer (best effort: not for another allocator's memory).
  *   p3d_pre_upfirdn_dev: out[i] = sum_q h[(pre_remove + i) down - up q] x[q], i < nout (scipy's resample_poly after its padding).
  *   p3d_pre_spectral_dev: forward FFT of x at length nt; Z[k] = op(fac[k] X[src[k] >> 2]) for k < num (op = src & 3: 0 plain, 1
  *       conjugate, 2 real part; src < 0: 0); inverse FFT at length num (unnormalised); out = |Z| * s1 (modulus) or Re Z * s1 * s2.
@@ -416,7 +419,7 @@ int p3d_pre_balance_dev(int device, const float* x_dev, size_t nt, size_t ntrace
 int p3d_pre_gain_dev(int device, const float* x_dev, size_t nt, size_t ntraces, const double* prm, const double* curves, float* out_dev,
                      float* work_dev);
 int p3d_pre_sosfiltfilt_dev(int device, const float* x_dev, size_t nt, size_t ntraces, int nsec, const double* sos, const double* zi, int padlen,
-                            float* out_dev, float* work_dev);
+                            float* out_dev, void* work_dev);
 int p3d_pre_upfirdn_dev(int device, const float* x_dev, size_t nt, size_t ntraces, const double* h, int nh, int up, int down, long long pre_remove,
                         size_t nout, float* out_dev);
 int p3d_pre_spectral_dev(int device, const float* x_dev, size_t nt, size_t ntraces, int num, const int* src, const float* fac, int modulus,

@@ -1764,9 +1764,10 @@ def trace_ops(x, ops, device=0, chunk_traces=None):
     for op in ops:
         lens.append(_op_len(op, lens[-1]))
     ntmax = max(lens)
-    pad = max([int(op[3]) for op in ops if op[0] == "filter"] or [0])
+    # the filter's extension: float32, or double for a cascade of more than 8 sections (include/p3d.h)
+    ext = max([(8 if np.shape(op[1])[0] > 8 else 4) * (ntmax + 2 * int(op[3])) for op in ops if op[0] == "filter"] or [0])
     # per trace: two float buffers, the work buffer (float / filter extension / two complex64 lines)
-    work_per_trace = max(4 * ntmax, 4 * (ntmax + 2 * pad), 8 * 2 * ntmax)
+    work_per_trace = max(4 * ntmax, ext, 8 * 2 * ntmax)
     per_trace = 2 * 4 * ntmax + work_per_trace
     chunk = chunk_traces or PRE_CHUNK_TRACES
     if not chunk:

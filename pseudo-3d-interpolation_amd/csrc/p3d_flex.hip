@@ -444,6 +444,24 @@ __device__ __forceinline__ void flex_pass_prime(const c32* A, c32* B, const c32*
 {
     const int total = COLS ? pa.nb << tsh : pa.nb;
     const int istr = COLS ? 1 << tsh : 1;
+    if (pa.nb == 1 && total < step) {
+        // the line length itself is the prime R: ONE butterfly per line, and one thread ran all R^2 terms of it (4.5 s for a
+        // 4001-point line).  Its R outputs go to different threads, each summed in the same order.  Passes with several butterflies
+        // per line (a factor 17 / 19 / 23 of a longer line) take the loop below, as before
+        for (int w = first; w < total * R; w += step) {
+            const int b = w / R, k = w - b * R;
+            const int j = COLS ? b >> tsh : b, l = COLS ? b & (istr - 1) : 0;
+            const int jq = pa.ns > 1 ? (int)__umulhi((unsigned)j, pa.mg) : j, jm = j - jq * pa.ns;
+            const int j0 = jq * pa.ns * R + jm;
+            c32 acc{0.f, 0.f};
+            for (int t = 0; t < R; ++t) {
+                const long idx = ((long)t * jm * pa.ts + (long)((long)t * k % R) * pa.nb) % n;
+                acc = acc + A[(size_t)(j + t * pa.nb) * istr + l] * conj_if<DIR>(tw[idx]);
+            }
+            B[(size_t)(j0 + k * pa.ns) * istr + l] = acc;
+        }
+        return;
+    }
     for (int b = first; b < total; b += step) {
         const int j = COLS ? b >> tsh : b, l = COLS ? b & (istr - 1) : 0;
         const int jq = pa.ns > 1 ? (int)__umulhi((unsigned)j, pa.mg) : j, jm = j - jq * pa.ns;

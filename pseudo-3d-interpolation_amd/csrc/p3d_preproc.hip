@@ -14,13 +14,15 @@
 //   sosfiltfilt (sos_*_kernel<NS>): scipy's odd extension (formed in float32, as scipy forms it on a float32 array), the forward
 //        cascade from zi * ext[0], the backward cascade from zi * y[-1], transposed direct form II in DOUBLE precision; the
 //        sections' state lives in registers (the section loop is unrolled for NS <= 8).  Longer cascades run in groups of 8
-//        sections, one pass per group (exact: sosfilt_zi already carries the gain of the earlier sections).
+//        sections, one pass per group (exact: sosfilt_zi already carries the gain of the earlier sections); the signal between
+//        the groups stays in DOUBLE (a float32 hand-off after every group cost 1.7e-5 rel-L2 at 17 band-pass sections).
 //   upfirdn (pre_upfirdn_kernel): one thread per (output sample, trace), taps in double, the window of scipy's resample_poly.
 //   spectral (resample / envelope): real -> complex, the any-length line FFT (axis0_fft, p3d_api.hip), a bin remap with factors,
 //        the inverse FFT at the output length, real part (resample) or modulus (envelope).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <vector>
 
 #include "p3d.h"
@@ -40,6 +42,23 @@ int check_shape(size_t nt, size_t ntr)
 {
     if (nt < 1 || ntr < 1) return fail(P3D_ERR_INVALID, "bad shape (nt %zu, ntraces %zu)", nt, ntr);
     if (ntr > 2147483647u) return fail(P3D_ERR_INVALID, "too many traces for one call: split the cube");
+    return P3D_OK;
+}
+
+// a caller's work buffer: aligned for its element, and long enough as far as the runtime can tell.  Best effort: the room is counted
+// to the end of the allocation that holds the pointer (for a view into a pooled block: to the end of that block), and a pointer the
+// runtime does not know is taken on trust
+int check_work(const void* work, size_t need, size_t align)
+{
+    if ((uintptr_t)work % align) return fail(P3D_ERR_INVALID, "work buffer not aligned to %zu bytes", align);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)work) != hipSuccess) {
+        (void)hipGetLastError();   // not an allocation of this runtime (a view of another allocator's pool): nothing to compare with
+        return P3D_OK;
+    }
+    const size_t room = size - (size_t)((const char*)work - (const char*)base);
+    if (room < need) return fail(P3D_ERR_INVALID, "work buffer too small: %zu bytes needed, %zu there", need, room);
     return P3D_OK;
 }
 
@@ -217,10 +236,10 @@ __global__ void __launch_bounds__(TPB) sos_fused_kernel(const float* __restrict_
     }
 }
 
-// one group of a longer cascade, forward: from the extension of x (first group) or in place on tmp; the last group also keeps
-// its last output in double (y0), where the backward cascade starts, as the fused kernel does
+// one group of a longer cascade, forward: from the extension of x (first group) or in place on tmp, which holds the signal
+// between the groups in double [nt + 2 edge][ntr]; the last group also keeps its last output (y0), where the backward cascade starts
 template <int NS>
-__global__ void __launch_bounds__(TPB) sos_fwd_kernel(const float* __restrict__ x, float* __restrict__ tmp, double* __restrict__ y0, SosArgs s,
+__global__ void __launch_bounds__(TPB) sos_fwd_kernel(const float* __restrict__ x, double* __restrict__ tmp, double* __restrict__ y0, SosArgs s,
                                                       long long nt, long long ntr, long long edge, int first, int last)
 {
     const long long j = (long long)blockIdx.x * TPB + threadIdx.x;
@@ -230,17 +249,17 @@ __global__ void __launch_bounds__(TPB) sos_fwd_kernel(const float* __restrict__ 
     st.init(s, (double)odd_ext_at(x, 0, nt, ntr, edge, j));   // every group starts from zi * ext[0] of the ORIGINAL input
     double y = 0.0;
     for (long long i = 0; i < ne; ++i) {
-        const double v = first ? (double)odd_ext_at(x, i, nt, ntr, edge, j) : (double)tmp[i * ntr + j];
+        const double v = first ? (double)odd_ext_at(x, i, nt, ntr, edge, j) : tmp[i * ntr + j];
         y = st.step(s, v);
-        tmp[i * ntr + j] = (float)y;
+        tmp[i * ntr + j] = y;
     }
     if (last) y0[j] = y;
 }
 
-// ... backward: in place on tmp from its end, from zi * y0 (y0: the last forward output of the cascade, in double);
+// ... backward: in place on tmp from its end, from zi * y0 (y0: the last forward output of the cascade);
 // the last group writes the interior to out
 template <int NS>
-__global__ void __launch_bounds__(TPB) sos_bwd_kernel(float* __restrict__ tmp, float* __restrict__ out, const double* __restrict__ y0, SosArgs s,
+__global__ void __launch_bounds__(TPB) sos_bwd_kernel(double* __restrict__ tmp, float* __restrict__ out, const double* __restrict__ y0, SosArgs s,
                                                       long long nt, long long ntr, long long edge, int last)
 {
     const long long j = (long long)blockIdx.x * TPB + threadIdx.x;
@@ -249,8 +268,8 @@ __global__ void __launch_bounds__(TPB) sos_bwd_kernel(float* __restrict__ tmp, f
     SosState<NS> st;
     st.init(s, y0[j]);
     for (long long i = ne - 1; i >= 0; --i) {
-        const double v = st.step(s, (double)tmp[i * ntr + j]);
-        if (!last) tmp[i * ntr + j] = (float)v;
+        const double v = st.step(s, tmp[i * ntr + j]);
+        if (!last) tmp[i * ntr + j] = v;
         else if (i >= edge && i < edge + nt) out[(i - edge) * ntr + j] = (float)v;
     }
 }
@@ -481,7 +500,7 @@ int p3d_pre_gain_dev(int device, const float* x, size_t nt, size_t ntr, const do
 }
 
 int p3d_pre_sosfiltfilt_dev(int device, const float* x, size_t nt, size_t ntr, int nsec, const double* sos, const double* zi, int padlen, float* out,
-                            float* work)
+                            void* work)
 {
     if (!x || !out || !sos || !zi) return fail(P3D_ERR_INVALID, "NULL buffer");
     if (x == out) return fail(P3D_ERR_INVALID, "x and out must be different buffers");
@@ -494,13 +513,17 @@ int p3d_pre_sosfiltfilt_dev(int device, const float* x, size_t nt, size_t ntr, i
     for (int k = 0; k < nsec; ++k)
         if (sos[6 * k + 3] != 1.0) return fail(P3D_ERR_INVALID, "section %d: a0 must be 1", k);
     const size_t ne = nt + 2 * (size_t)padlen;
-    DevBuf dtmp, dy0;
-    float* tmp = work;
-    if (!tmp) {
-        P3D_TRY(hipMalloc(&dtmp.p, sizeof(float) * ne * ntr));
-        tmp = (float*)dtmp.p;
-    }
     const int ngroups = (nsec + SOS_GROUP - 1) / SOS_GROUP;
+    // the intermediate: float32 for one group (between the forward and the backward pass), double between the groups of a longer cascade
+    const size_t need = (ngroups == 1 ? sizeof(float) : sizeof(double)) * ne * ntr;
+    DevBuf dtmp, dy0;
+    void* tmp = work;
+    if (!tmp) {
+        P3D_TRY(hipMalloc(&dtmp.p, need));
+        tmp = dtmp.p;
+    } else {
+        if ((rc = check_work(tmp, need, ngroups == 1 ? sizeof(float) : sizeof(double)))) return rc;
+    }
     std::vector<SosArgs> groups(ngroups);
     std::vector<int> gsize(ngroups);
     for (int g = 0; g < ngroups; ++g) {
@@ -517,14 +540,15 @@ int p3d_pre_sosfiltfilt_dev(int device, const float* x, size_t nt, size_t ntr, i
     const dim3 g1((unsigned)((ntr + TPB - 1) / TPB));
     const long long lnt = (long long)nt, lntr = (long long)ntr, ledge = padlen;
     if (ngroups == 1) {
-        P3D_TRY(launch_ns<FusedL>(gsize[0], g1, x, tmp, out, groups[0], lnt, lntr, ledge));
+        P3D_TRY(launch_ns<FusedL>(gsize[0], g1, x, (float*)tmp, out, groups[0], lnt, lntr, ledge));
     } else {
         P3D_TRY(hipMalloc(&dy0.p, sizeof(double) * ntr));
         double* y0 = (double*)dy0.p;
+        double* dt = (double*)tmp;
         for (int g = 0; g < ngroups; ++g)
-            P3D_TRY(launch_ns<FwdL>(gsize[g], g1, x, tmp, y0, groups[g], lnt, lntr, ledge, (int)(g == 0), (int)(g == ngroups - 1)));
+            P3D_TRY(launch_ns<FwdL>(gsize[g], g1, x, dt, y0, groups[g], lnt, lntr, ledge, (int)(g == 0), (int)(g == ngroups - 1)));
         for (int g = 0; g < ngroups; ++g)
-            P3D_TRY(launch_ns<BwdL>(gsize[g], g1, tmp, out, (const double*)y0, groups[g], lnt, lntr, ledge, (int)(g == ngroups - 1)));
+            P3D_TRY(launch_ns<BwdL>(gsize[g], g1, dt, out, (const double*)y0, groups[g], lnt, lntr, ledge, (int)(g == ngroups - 1)));
     }
     P3D_TRY(hipDeviceSynchronize());
     return P3D_OK;

@@ -42,7 +42,7 @@ def main():
         x.upload(rng.standard_normal((min(64, nt - r0), ntr), dtype=np.float32), first=r0)
     out = _ffi.DeviceArray((2 * nt, ntr), np.float32)
     ref = _ffi.DeviceArray((ntr,), np.float32)
-    work = _ffi.DeviceArray((4 * nt * ntr,), np.float32)        # 16 B/pt: two complex64 lines, or the filter's extension
+    work = _ffi.DeviceArray((4 * nt * ntr,), np.float32)        # 16 B/pt: two complex64 lines, or the filter's extension (doubles above 8 sections)
     twt = np.arange(nt) * 0.0005
     prm, curves = S.gain_tables(nt, twt, tpow=2.0, epow=0.5, gpow=0.5, clip=2.0, pclip=1.5, nclip=-1.5)
 
@@ -71,7 +71,7 @@ def main():
          lambda: chk(lib.p3d_pre_gain_dev(0, x.ptr, nt, ntr, ptr(prm), ptr(curves), out.ptr, work.ptr))),
         ('balance rms', 12, 1.5, lambda: chk(lib.p3d_pre_balance_dev(0, x.ptr, nt, ntr, 0, out.ptr, ref.ptr))),
         (f'sosfiltfilt {ns3} sections', 16, 3.0, f3),
-        (f'sosfiltfilt {ns10} sections', 16 + 8, None, f10),
+        (f'sosfiltfilt {ns10} sections', 12 + 16 + 16 + 12, None, f10),      # two groups, the signal between them in double
         ('resample_poly down 2', 4 + 2, 1.0, pd2),
         ('resample_poly up 2', 4 + 8, None, pu2),
         ('resample (FFT) down 2', 4 + 2, None, spectral(S.resample_op(nt, nt // 2, 'hann'))),
