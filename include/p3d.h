@@ -63,6 +63,12 @@ extern "C" {
 /* p3d_pocs_params.flags */
 #define P3D_FLAG_PROFILE 1 /* bracket every kernel launch with HIP events; read with p3d_last_profile() */
 #define P3D_FLAG_PRIMED 2  /* p3d_pocs_prime_dev has just run on exactly this cube and mask: p3d_pocs_run_dev may skip its first pass */
+/* `mask` holds one mask PER SLICE, [nslices][nil][nxl] (float32 for the float32 loops, double for the *64 loops; host or device exactly as the entry point
+ * takes its shared mask): slice s is interpolated with mask[s], as POCS_algorithm(x[s], mask[s], ...) would.  Honoured by every run entry point that takes
+ * p3d_pocs_params; p3d_multi_run hands each device's block its own part of the mask.  The float32 FFT loop then runs its unfused passes (fft2 | threshold |
+ * ifft2 | update) for every shape -- the fused paths rest on packed forms of one mask.  P3D_FLAG_PRIMED is ignored together with this flag: the primed
+ * first pass packs one mask.  Plans grow their mask buffers to max_slices slices when the flag is first seen. */
+#define P3D_FLAG_MASK_PER_SLICE 4
 
 typedef struct p3d_plan p3d_plan;
 
@@ -157,9 +163,11 @@ int p3d_pocs_stats(p3d_plan* plan, const void* x_host, int dtype, int nslices, d
 int p3d_pocs_sorted_spectrum(p3d_plan* plan, const void* x, int nslices, float* peaks_host);
 int p3d_pocs_data_driven_pick(p3d_plan* plan, int nslices, int niter, const float* bounds_host, float* tau_host, int64_t* count_host);
 
-/* The POCS loop (POCS.py:549-632) for a batch of slices sharing one trace mask.
+/* The POCS loop (POCS.py:549-632) for a batch of slices sharing one trace mask, or bringing one mask each (P3D_FLAG_MASK_PER_SLICE).
  *   x        [nslices][nil][nxl] observed data, zeros at missing traces, dtype as given
- *   mask     [nil][nxl] float32, 1 = observed trace, 0 = missing (cube_POCS_interpolation_3D.py:242-244)
+ *   mask     [nil][nxl] float32, 1 = observed trace, 0 = missing (cube_POCS_interpolation_3D.py:242-244), shared by the batch; with
+ *            P3D_FLAG_MASK_PER_SLICE in params->flags [nslices][nil][nxl], one mask per slice (the same holds for the `mask` of every
+ *            other *_run entry point below, float32 or double as documented there)
  *   tau      HOST, [nslices][niter][2] doubles: Re, Im of the threshold used at each iteration
  *            (decay[k], or sqrt(decay[k]) for sqrt_decay; POCS.py:595)
  *   active   HOST, [nslices] uint8 or NULL: 0 marks an all-zero slice, which the reference returns

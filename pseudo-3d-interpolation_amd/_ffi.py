@@ -20,6 +20,7 @@ P3D_OP.update({f"{k}-percentile": v | P3D_OP_PERCENTILE for k, v in list(P3D_OP.
 P3D_VER = {"regular": 0, "fast": 1, "adaptive": 2}
 P3D_FLAG_PROFILE = 1
 P3D_FLAG_PRIMED = 2
+P3D_FLAG_MASK_PER_SLICE = 4
 STATS_PER_SLICE = 6
 P3D_DCT_NORM = {None: 0, "backward": 0, "ortho": 1}   # P3D_DCT_BACKWARD / P3D_DCT_ORTHO: the `norm` of scipy.fft.dctn / idctn
 
@@ -399,20 +400,21 @@ class _PlanBase:
         return ()
 
     def _host_job(self, x, mask):
-        """The host cube as the library takes it, its dtype code, the mask in the plan's precision and an empty result."""
+        """The host cube as the library takes it, its dtype code, the mask in the plan's precision -- (nil, nxl), shared by the batch, or
+        (nslices, nil, nxl), one mask per slice (P3D_FLAG_MASK_PER_SLICE) -- and an empty result."""
         xc, dt = self._cube(x)
         m = np.ascontiguousarray(mask, dtype=self._MASK_DT)
-        if m.shape != (self.nil, self.nxl):
+        if m.shape != (self.nil, self.nxl) and m.shape != xc.shape:
             raise ValueError(f"mask shape {m.shape} != {(self.nil, self.nxl)}")
         return xc, dt, m, np.empty_like(xc)
 
     def _run_entry(self, entry, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op, version, eps, alpha, active, profile=False, want_sums=True,
-                   primed=False, extra=()):
+                   primed=False, extra=(), mask_per_slice=False):
         """One call of a p3d_*_run entry on raw pointers (``extra``: what the entry takes behind the common arguments).  Returns (niter_done, sums or
         None, device ms of the loop)."""
         t = _tau_table(tau, (n, niter) + self._tau_shape())
         act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        prm = Plan._params(niter, thresh_op, version, eps, alpha, profile, primed)
+        prm = Plan._params(niter, thresh_op, version, eps, alpha, profile, primed, mask_per_slice)
         done = np.zeros(n, np.int32)
         sums = np.zeros((niter + 1, n), np.float64) if want_sums else None
         ms = C.c_double(0.0)
@@ -430,12 +432,15 @@ class _PlanBase:
         iteration, real or complex.  Returns (out, niter_done, sums, elapsed_ms)."""
         xc, dt, m, out = self._host_job(x, mask)
         done, sums, ms = self.run_dev(xc.ctypes.data, dt, m.ctypes.data, tau, niter, out.ctypes.data, xc.shape[0], thresh_op=thresh_op, version=version,
-                                      eps=eps, alpha=alpha, active=active)
+                                      eps=eps, alpha=alpha, active=active, mask_per_slice=m.ndim == 3)
         return out, done, sums, ms
 
-    def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
-        """`run` on raw pointers (host or device; the mask in the plan's precision, [nil][nxl]).  Returns (niter_done, sums, device ms of the loop)."""
-        return self._run_entry(self._RUN, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op, version, eps, alpha, active)
+    def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None,
+                mask_per_slice=False):
+        """`run` on raw pointers (host or device; the mask in the plan's precision, [nil][nxl], or [n][nil][nxl] with ``mask_per_slice``).  Returns
+        (niter_done, sums, device ms of the loop)."""
+        return self._run_entry(self._RUN, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op, version, eps, alpha, active,
+                               mask_per_slice=mask_per_slice)
 
 
 class _PlanBase64(_PlanBase):
@@ -677,11 +682,12 @@ class Plan(_PlanBase):
         return st
 
     @staticmethod
-    def _params(niter, thresh_op, version, eps, alpha, profile, primed=False):
+    def _params(niter, thresh_op, version, eps, alpha, profile, primed=False, mask_per_slice=False):
         if thresh_op not in P3D_OP:
             raise UnsupportedError(P3D_ERR_UNSUPPORTED, f"thresh_op {thresh_op!r} is not implemented by the HIP kernels")
         return PocsParams(int(niter), P3D_OP[thresh_op], P3D_VER[version],
-                          (P3D_FLAG_PROFILE if profile else 0) | (P3D_FLAG_PRIMED if primed else 0), float(eps), float(alpha))
+                          (P3D_FLAG_PROFILE if profile else 0) | (P3D_FLAG_PRIMED if primed else 0) | (P3D_FLAG_MASK_PER_SLICE if mask_per_slice else 0),
+                          float(eps), float(alpha))
 
     @staticmethod
     def _tau(tau, nslices, niter):
@@ -689,10 +695,10 @@ class Plan(_PlanBase):
 
     def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None,
             profile=False):
-        """Host arrays in, host arrays out.  Returns (out, niter_done, sums, elapsed_ms)."""
+        """Host arrays in, host arrays out; ``mask`` (nil, nxl) or, one per slice, (nslices, nil, nxl).  Returns (out, niter_done, sums, elapsed_ms)."""
         xc, dt, m, out = self._host_job(x, mask)
         done, sums, ms = self._run_entry("p3d_pocs_run", _ptr(xc), dt, _ptr(m), tau, niter, _ptr(out), xc.shape[0], thresh_op, version, eps, alpha,
-                                         active, profile)
+                                         active, profile, mask_per_slice=m.ndim == 3)
         return out, done, sums, ms
 
     def prime_dev(self, x_ptr, dtype, mask_ptr, nslices):
@@ -708,10 +714,11 @@ class Plan(_PlanBase):
         return st
 
     def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, nslices, thresh_op="hard", version="regular",
-                eps=0.0, alpha=1.0, active=None, profile=False, want_sums=True, primed=False):
-        """Device pointers in/out (cube stays resident in HBM).  Returns (niter_done, sums -- None unless ``want_sums`` --, elapsed_ms)."""
+                eps=0.0, alpha=1.0, active=None, profile=False, want_sums=True, primed=False, mask_per_slice=False):
+        """Device pointers in/out (cube stays resident in HBM); ``mask_per_slice``: ``mask_ptr`` holds [nslices][nil][nxl] (the unfused passes; ``primed``
+        is then ignored).  Returns (niter_done, sums -- None unless ``want_sums`` --, elapsed_ms)."""
         return self._run_entry("p3d_pocs_run_dev", x_ptr, dtype, mask_ptr, tau, niter, out_ptr, nslices, thresh_op, version, eps, alpha, active, profile,
-                               want_sums, primed)
+                               want_sums, primed, mask_per_slice=mask_per_slice)
 
     # ---- transform_kind = 'DCT': scipy.fft.dctn / idctn (type 2) as the transform of the loop ------------
     @staticmethod
@@ -755,14 +762,14 @@ class Plan(_PlanBase):
         """`run` with the DCT pair as the transform.  Returns (out, niter_done, sums, elapsed_ms)."""
         xc, dt, m, out = self._host_job(x, mask)
         done, sums, ms = self._run_entry("p3d_pocs_dct_run", _ptr(xc), dt, _ptr(m), tau, niter, _ptr(out), xc.shape[0], thresh_op, version, eps, alpha,
-                                         active, extra=(self._dct_norm(norm),))
+                                         active, extra=(self._dct_norm(norm),), mask_per_slice=m.ndim == 3)
         return out, done, sums, ms
 
     def dct_run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, nslices, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None,
-                    norm=None, want_sums=True):
+                    norm=None, want_sums=True, mask_per_slice=False):
         """`run_dev` with the DCT pair as the transform.  Returns (niter_done, sums, elapsed_ms)."""
         return self._run_entry("p3d_pocs_dct_run_dev", x_ptr, dtype, mask_ptr, tau, niter, out_ptr, nslices, thresh_op, version, eps, alpha, active,
-                               want_sums=want_sums, extra=(self._dct_norm(norm),))
+                               want_sums=want_sums, extra=(self._dct_norm(norm),), mask_per_slice=mask_per_slice)
 
     def last_sparsity(self):
         """Fraction of 8-column spectrum blocks that kept a coefficient in the last run (-1: dense path)."""
@@ -1674,15 +1681,15 @@ def multi_stats(x, devices):
 
 def multi_run(x, mask, tau, niter, devices, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
     """p3d_multi_run: the POCS loop on a host cube, blocks of slices on the listed devices (one process, one thread and one plan
-    per entry).  Returns (out, niter_done, sums)."""
+    per entry); ``mask`` (nil, nxl) or, one per slice, (nslices, nil, nxl).  Returns (out, niter_done, sums)."""
     xc, dt = _host_cube(x)
     n, nil, nxl = xc.shape
     m = np.ascontiguousarray(mask, dtype=np.float32)
-    if m.shape != (nil, nxl):
+    if m.shape != (nil, nxl) and m.shape != xc.shape:
         raise ValueError(f"mask shape {m.shape} != {(nil, nxl)}")
     t = _tau_table(tau, (n, niter))
     act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-    prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
+    prm = Plan._params(niter, thresh_op, version, eps, alpha, False, mask_per_slice=m.ndim == 3)
     dev = np.ascontiguousarray(devices, dtype=np.int32)
     out = np.empty_like(xc)
     done = np.zeros(n, np.int32)

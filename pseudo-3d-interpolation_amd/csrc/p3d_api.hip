@@ -317,7 +317,7 @@ struct p3d_plan {
     int device = 0;
     int nil = 0, nxl = 0, max_slices = 0;
     hipStream_t stream = nullptr;
-    p3d_plan* pct_plan = nullptr;      // generic twin of a tuned plan, created on first use of a percentile operator
+    p3d_plan* pct_plan = nullptr;      // generic twin of a tuned plan, created on first use of a percentile operator or of a per-slice mask
     unsigned* pct_sel = nullptr;       // [2][max_slices][8] radix-select state
     unsigned* pct_hist = nullptr;      // [max_slices][2048]
     float* pct_frac = nullptr;         // [max_slices]
@@ -369,6 +369,7 @@ struct p3d_plan {
     void* st_x = nullptr;
     void* st_out = nullptr;
     float* st_mask = nullptr;
+    size_t st_mask_cap = 0;   // elements: one slice until the first P3D_FLAG_MASK_PER_SLICE job through a host-pointer entry point, then max_slices slices
     size_t st_cap = 0;
     // p3d_pocs_prime_dev: the first pass of a job run ahead of it (statistics + work buffer + compact samples of exactly this cube)
     struct Primed { bool valid = false; const void* x = nullptr; const float* mask = nullptr; int dtype = 0, nslices = 0, nonbinary = 0, violation = 0; unsigned nobs = 0;
@@ -761,6 +762,15 @@ static ColArgs col_args(p3d_plan* p, int nslices)
     return c;
 }
 
+// the host mask of a job into st_mask: [nil][nxl], or with P3D_FLAG_MASK_PER_SLICE [nslices][nil][nxl] (the buffer then grows to max_slices slices, once)
+static int stage_host_mask(p3d_plan* p, const float* mask, const p3d_pocs_params* prm, int nslices)
+{
+    const bool per_slice = prm && (prm->flags & P3D_FLAG_MASK_PER_SLICE) != 0;
+    if (int rc = grow(p->st_mask, p->st_mask_cap, p->slice_elems() * (per_slice ? (size_t)p->max_slices : 1))) return rc;
+    P3D_TRY(hipMemcpy(p->st_mask, mask, sizeof(float) * p->slice_elems() * (per_slice ? (size_t)nslices : 1), hipMemcpyHostToDevice));
+    return P3D_OK;
+}
+
 static int ensure_staging(p3d_plan* p, size_t bytes_per_cube)
 {
     if (p->st_cap >= bytes_per_cube && p->st_x) return P3D_OK;
@@ -770,7 +780,8 @@ static int ensure_staging(p3d_plan* p, size_t bytes_per_cube)
     p->st_cap = 0;
     P3D_TRY(hipMalloc(&p->st_x, bytes_per_cube));
     P3D_TRY(hipMalloc(&p->st_out, bytes_per_cube));
-    if (!p->st_mask) P3D_TRY(hipMalloc((void**)&p->st_mask, sizeof(float) * p->slice_elems()));
+    if (!p->st_mask)
+        if (int rc = grow(p->st_mask, p->st_mask_cap, p->slice_elems())) return rc;
     p->st_cap = bytes_per_cube;
     return P3D_OK;
 }
@@ -1201,7 +1212,7 @@ int p3d_pocs_stats_dev(p3d_plan* p, const void* x, int dtype, int nslices, doubl
     P3D_TRY(hipSetDevice(p->device));
     if (p->generic) {
         P3D_TRY(hipMemsetAsync(p->rowsum, 0, sizeof(double) * nslices, p->stream));
-        P3D_TRY(gen_launch_update(p->work, x, dtype, nullptr, nullptr, p->rowsum, 0, 0, 0, 1.0f, nslices, p->slice_elems(), nullptr, 0,
+        P3D_TRY(gen_launch_update(p->work, x, dtype, nullptr, 0, nullptr, p->rowsum, 0, 0, 0, 1.0f, nslices, p->slice_elems(), nullptr, 0,
                                   p->stream));
         if ((rc = gen_fft2(p, p->work, p->work, nslices, 0, nullptr))) return rc;
         P3D_TRY(gen_launch_stats(p->work, p->partials, nslices, p->slice_elems(), p->tiles, p->stream));
@@ -1239,6 +1250,7 @@ struct RunJob {
     const void* x;
     int dtype;
     const float* mask;
+    size_t mask_stride;   // P3D_FLAG_MASK_PER_SLICE: nil * nxl (run_generic only), else 0
     const double* tau;
     const p3d_pocs_params* prm;
     void* out;
@@ -1266,7 +1278,7 @@ static int run_generic(RunJob& j)
     int rc;
     const size_t per_slice = p->slice_elems();
     const int* done_d = (early || j.frame.any_off()) ? p->done : nullptr;
-    P3D_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, nslices, per_slice,
+    P3D_TRY(gen_launch_update(p->work, x, dtype, mask, j.mask_stride, out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, nslices, per_slice,
                               done_d, 0, p->stream));
     for (int k = 0; k < niter; ++k) {
         const bool last = k + 1 == niter;
@@ -1291,7 +1303,7 @@ static int run_generic(RunJob& j)
         }
         P3D_TRY(gen_launch_shrink(p->work, p->tau, niter, k, base_op, nslices, per_slice, done_d, p->stream));
         if ((rc = gen_fft2(p, p->work, p->work, nslices, 1, done_d))) return rc;
-        P3D_TRY(gen_launch_update(p->work, x, dtype, mask, out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0,
+        P3D_TRY(gen_launch_update(p->work, x, dtype, mask, j.mask_stride, out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0,
                                   (early || last) ? 1 : 0, (float)prm->alpha, nslices, per_slice, p->done, last ? 1 : 0, p->stream));
         if (early) conv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
     }
@@ -1639,7 +1651,8 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
 {
     // P3D_FLAG_PRIMED: the caller says p3d_pocs_prime_dev has just run on exactly this cube and mask -- believed only if the plan
     // agrees (same pointers, type and batch, nothing else on the plan in between)
-    const bool primed_in = p && prm && (prm->flags & P3D_FLAG_PRIMED) && p->primed.valid && p->primed.x == x && p->primed.mask == mask &&
+    const bool per_slice_mask = prm && (prm->flags & P3D_FLAG_MASK_PER_SLICE) != 0;   // (never primed: the primed first pass packs ONE mask)
+    const bool primed_in = p && prm && (prm->flags & P3D_FLAG_PRIMED) && !per_slice_mask && p->primed.valid && p->primed.x == x && p->primed.mask == mask &&
                            p->primed.dtype == dtype && p->primed.nslices == nslices;
     const p3d_plan::Primed primed_state = p ? p->primed : p3d_plan::Primed{};
     int rc = check_batch(p, nslices);
@@ -1672,7 +1685,7 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
             p->prof_events.push_back(e);
         }
     }
-    RunJob j{p, x, dtype, mask, tau, prm, out, nslices, niter_done, sums, elapsed_ms, base_op, percentile, sw, LoopFrame(p, active, nslices, niter)};
+    RunJob j{p, x, dtype, mask, per_slice_mask ? p->slice_elems() : 0, tau, prm, out, nslices, niter_done, sums, elapsed_ms, base_op, percentile, sw, LoopFrame(p, active, nslices, niter)};
     P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
     if ((rc = j.frame.begin())) return rc;
 
@@ -1680,7 +1693,9 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
     // where the column-blocked work buffer holds exactly the slice (no padding columns): the column pass is split into forward
     // transform | rank + threshold | inverse transform.  Otherwise:
     const bool pct_fused = percentile && !p->generic && !sw.no_pct_fused && wk_slice_stride(p->nil, p->nxl) == p->slice_elems();
-    if (percentile && !p->generic && !pct_fused) {
+    // A per-slice mask (P3D_FLAG_MASK_PER_SLICE) takes the same way for every shape and operator: the fused, column-pipe, resident and half-spectrum paths
+    // all rest on packed forms of ONE mask (pack_mask*, the lane-mask tables, the compact observed samples, rowbase)
+    if (!p->generic && (per_slice_mask || (percentile && !pct_fused))) {
         // the tuned kernels never materialise the spectrum; ranking it needs the unfused pipeline -> a second, generic plan
         if (!p->pct_plan) {
             p3d_plan* q = nullptr;
@@ -1725,7 +1740,7 @@ int p3d_pocs_run(p3d_plan* p, const void* x, int dtype, const float* mask, const
     const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
     const size_t bytes = esz * p->slice_elems() * nslices;
     P3D_TRY(hipMemcpy(p->st_x, x, bytes, hipMemcpyHostToDevice));
-    P3D_TRY(hipMemcpy(p->st_mask, mask, sizeof(float) * p->slice_elems(), hipMemcpyHostToDevice));
+    if ((rc = stage_host_mask(p, mask, prm, nslices))) return rc;
     if ((rc = p3d_pocs_run_dev(p, p->st_x, dtype, p->st_mask, tau, active, prm, p->st_out, nslices, niter_done, sums,
                                elapsed_ms)))
         return rc;
@@ -1777,7 +1792,7 @@ static int dct_check(p3d_plan* p, int nslices, int norm)
 static int dct_forward(p3d_plan* p, const void* x, int dtype, int nslices, int norm, double* sums)
 {
     c32* const W = dct_buf(p);
-    P3D_TRY(dct_launch_update(W, x, dtype, nullptr, nullptr, sums, 0, 0, 0, 1.0f, nslices, p->nil, p->nxl, nullptr, 0, p->stream));
+    P3D_TRY(dct_launch_update(W, x, dtype, nullptr, 0, nullptr, sums, 0, 0, 0, 1.0f, nslices, p->nil, p->nxl, nullptr, 0, p->stream));
     if (int rc = fft2_enqueue(p, W, W, nslices, 0)) return rc;
     P3D_TRY(dct_launch_group(DCT_COMBINE, W, dct_tab(p, norm), nullptr, 1, 0, 0, nslices, p->nil, p->nxl, nullptr, p->stream));
     return P3D_OK;
@@ -1798,7 +1813,7 @@ int p3d_dct2_c64_dev(p3d_plan* p, const void* in, void* out, int nslices, int in
         P3D_TRY(hipMemcpyAsync(W, in, bytes, hipMemcpyDeviceToDevice, p->stream));
         P3D_TRY(dct_launch_group(DCT_SPLIT, W, dct_tab(p, norm), nullptr, 1, 0, 0, nslices, p->nil, p->nxl, nullptr, p->stream));
         if ((rc = fft2_enqueue(p, W, W, nslices, 1))) return rc;
-        P3D_TRY(dct_launch_update(W, nullptr, P3D_C64, nullptr, out, nullptr, 2, 0, 0, 1.0f, nslices, p->nil, p->nxl, nullptr, 0, p->stream));
+        P3D_TRY(dct_launch_update(W, nullptr, P3D_C64, nullptr, 0, out, nullptr, 2, 0, 0, 1.0f, nslices, p->nil, p->nxl, nullptr, 0, p->stream));
     }
     P3D_TRY(hipStreamSynchronize(p->stream));
     return P3D_OK;
@@ -1893,7 +1908,8 @@ int p3d_pocs_dct_run_dev(p3d_plan* p, const void* x, int dtype, const float* mas
     c32* const W = dct_buf(p);
     const DctTab tab = dct_tab(p, norm);
     const float alpha = (float)prm->alpha;
-    P3D_TRY(dct_launch_update(W, x, dtype, mask, out, p->sums, 0, adaptive ? 1 : 0, 0, alpha, nslices, n1, n2, done_d, 0, p->stream));
+    const size_t mask_stride = (prm->flags & P3D_FLAG_MASK_PER_SLICE) ? per_slice : 0;
+    P3D_TRY(dct_launch_update(W, x, dtype, mask, mask_stride, out, p->sums, 0, adaptive ? 1 : 0, 0, alpha, nslices, n1, n2, done_d, 0, p->stream));
     std::vector<unsigned> sel_h;
     std::vector<float> frac_h;
     for (int k = 0; k < niter; ++k) {
@@ -1922,7 +1938,7 @@ int p3d_pocs_dct_run_dev(p3d_plan* p, const void* x, int dtype, const float* mas
             P3D_TRY(dct_launch_group(DCT_FUSED, W, tab, p->tau, niter, k, base_op, nslices, n1, n2, done_d, p->stream));
         }
         if ((rc = fft2_enqueue(p, W, W, nslices, 1))) return rc;
-        P3D_TRY(dct_launch_update(W, x, dtype, mask, out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0,
+        P3D_TRY(dct_launch_update(W, x, dtype, mask, mask_stride, out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0,
                                   alpha, nslices, n1, n2, p->done, last ? 1 : 0, p->stream));
         if (early) conv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
     }
@@ -1944,7 +1960,7 @@ int p3d_pocs_dct_run(p3d_plan* p, const void* x, int dtype, const float* mask, c
     const size_t esz = dtype == P3D_C64 ? sizeof(c32) : sizeof(float);
     const size_t bytes = esz * p->slice_elems() * nslices;
     P3D_TRY(hipMemcpy(p->st_x, x, bytes, hipMemcpyHostToDevice));
-    P3D_TRY(hipMemcpy(p->st_mask, mask, sizeof(float) * p->slice_elems(), hipMemcpyHostToDevice));
+    if ((rc = stage_host_mask(p, mask, prm, nslices))) return rc;
     if ((rc = p3d_pocs_dct_run_dev(p, p->st_x, dtype, p->st_mask, tau, active, prm, p->st_out, nslices, niter_done, sums, elapsed_ms, norm))) return rc;
     P3D_TRY(hipMemcpy(out, p->st_out, bytes, hipMemcpyDeviceToHost));
     return P3D_OK;
@@ -2188,6 +2204,7 @@ int p3d_multi_run(int ndev, const int* devices, int nil, int nxl, const void* x,
     if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter = %d", prm->niter);
     const size_t per = (size_t)nil * nxl * (dtype == P3D_C64 ? sizeof(c32) : sizeof(float));
     const int niter = prm->niter;
+    const size_t mask_step = (prm->flags & P3D_FLAG_MASK_PER_SLICE) ? (size_t)nil * nxl : 0;   // every chunk takes its own part of a per-slice mask
     return run_blocks(ndev, devices, nslices, [&](BlockJob& j) -> int {
         const int step = chunk_slices(nil, nxl, j.hi - j.lo);
         p3d_plan* plan = nullptr;
@@ -2195,7 +2212,7 @@ int p3d_multi_run(int ndev, const int* devices, int nil, int nxl, const void* x,
         std::vector<double> part(sums ? (size_t)(niter + 1) * step : 0);
         for (int lo = j.lo; rc == P3D_OK && lo < j.hi; lo += step) {
             const int n = std::min(step, j.hi - lo);
-            rc = p3d_pocs_run(plan, (const char*)x + per * lo, dtype, mask, tau + (size_t)2 * niter * lo, active ? active + lo : nullptr, prm,
+            rc = p3d_pocs_run(plan, (const char*)x + per * lo, dtype, mask + mask_step * lo, tau + (size_t)2 * niter * lo, active ? active + lo : nullptr, prm,
                               (char*)out + per * lo, n, niter_done ? niter_done + lo : nullptr, sums ? part.data() : nullptr, nullptr);
             if (rc == P3D_OK && sums)   // [(niter + 1)][n] of this chunk -> columns lo .. lo + n of [(niter + 1)][nslices]
                 for (int k = 0; k <= niter; ++k) std::memcpy(sums + (size_t)k * nslices + lo, part.data() + (size_t)k * n, sizeof(double) * n);

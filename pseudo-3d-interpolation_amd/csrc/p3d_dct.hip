@@ -89,7 +89,7 @@ __device__ inline double dct_block_sum(double v, double* sh)
 }
 
 // gen_update_kernel (p3d_generic.hip) with w addressed through the reordering; the arithmetic is the same, expression for expression
-__global__ __launch_bounds__(256) void dct_update_kernel(c32* w, const void* x, int dtype, const float* mask, void* out, double* sums, int mode,
+__global__ __launch_bounds__(256) void dct_update_kernel(c32* w, const void* x, int dtype, const float* mask, size_t mask_stride, void* out, double* sums, int mode,
                                                          int adaptive, int write_out, float alpha, int n1, int n2, const int* done, int zero_fill)
 {
     __shared__ double sh[256];
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void dct_update_kernel(c32* w, const void* x, 
         c32 xo;
         if (dtype == 0) xo = reinterpret_cast<const c32*>(x)[g];
         else xo = c32{reinterpret_cast<const float*>(x)[g], 0.f};
-        const float m = mask ? mask[i] : 0.f;
+        const float m = mask ? mask[(size_t)s * mask_stride + i] : 0.f;
         const float wgt = 1.0f - alpha * m;
         c32 xn;
         if (mode == 0) {
@@ -156,12 +156,12 @@ hipError_t dct_launch_group(int mode, c32* w, const DctTab& tab, const c32* tau,
     return hipGetLastError();
 }
 
-hipError_t dct_launch_update(c32* w, const void* x, int dtype, const float* mask, void* out, double* sums, int mode, int adaptive, int write_out,
+hipError_t dct_launch_update(c32* w, const void* x, int dtype, const float* mask, size_t mask_stride, void* out, double* sums, int mode, int adaptive, int write_out,
                              float alpha, int nslices, int n1, int n2, const int* done, int zero_fill, hipStream_t st)
 {
     const size_t per_slice = (size_t)n1 * n2;
     const unsigned bx = (unsigned)((per_slice + 255) / 256 < 256 ? (per_slice + 255) / 256 : 256);
-    dct_update_kernel<<<dim3(bx, nslices), 256, 0, st>>>(w, x, dtype, mask, out, sums, mode, adaptive, write_out, alpha, n1, n2, done, zero_fill);
+    dct_update_kernel<<<dim3(bx, nslices), 256, 0, st>>>(w, x, dtype, mask, mask_stride, out, sums, mode, adaptive, write_out, alpha, n1, n2, done, zero_fill);
     return hipGetLastError();
 }
 

@@ -25,7 +25,7 @@ hipError_t dct_launch_group(int mode, c32* w, const DctTab& tab, const c32* tau,
 
 // gen_launch_update (p3d_generic.hpp) with the even/odd reordering of both axes folded into the addressing of w: sample (i1, i2) of x, mask
 // and out lives at w[perm(n1, i1)][perm(n2, i2)].  mode 0 / 1 as there; mode 2: out = w through the reordering, nothing else (complex64)
-hipError_t dct_launch_update(c32* w, const void* x, int dtype, const float* mask, void* out, double* sums, int mode, int adaptive, int write_out,
+hipError_t dct_launch_update(c32* w, const void* x, int dtype, const float* mask, size_t mask_stride, void* out, double* sums, int mode, int adaptive, int write_out,
                              float alpha, int nslices, int n1, int n2, const int* done, int zero_fill, hipStream_t st);
 
 }  // namespace p3d

@@ -33,6 +33,7 @@ using p3d::choose_out;
 using p3d::elem_bytes;
 using p3d::grow;
 using p3d::LoopFrame;
+using p3d::stage_mask;
 using p3d::take_x;
 
 namespace {
@@ -163,7 +164,7 @@ __device__ inline double block_sum64(double v, double* sh)
 // per (slice, block) partial sums of |x| (fixed order: the host adds the blocks of a slice in order -- reproducible costs)
 // mode 0: first input (w = x or its APOCS mix); mode 1: re-insertion (POCS.py:616-619), optional store of the iterate, APOCS mix
 // dtype: P3D_C128 complex128 / P3D_F64 float64 / P3D_C64 complex64 / P3D_F32 float32 (of x and out; the arithmetic is double either way)
-__global__ void update64_kernel(c64* w, const void* x, int dtype, const double* mask, void* out, double* partial, int mode, int adaptive, int write_out,
+__global__ void update64_kernel(c64* w, const void* x, int dtype, const double* mask, size_t mask_stride, void* out, double* partial, int mode, int adaptive, int write_out,
                                 double alpha, size_t per_slice, const int* done, int zero_fill)
 {
     __shared__ double sh[256];
@@ -190,7 +191,7 @@ __global__ void update64_kernel(c64* w, const void* x, int dtype, const double* 
         else if (dtype == P3D_F64) xo = c64{reinterpret_cast<const double*>(x)[g], 0.0};
         else if (dtype == P3D_C64) { const float2 t = reinterpret_cast<const float2*>(x)[g]; xo = c64{(double)t.x, (double)t.y}; }
         else xo = c64{(double)reinterpret_cast<const float*>(x)[g], 0.0};
-        const double m = mask ? mask[i] : 0.0;
+        const double m = mask ? mask[(size_t)s * mask_stride + i] : 0.0;
         const double wgt = 1.0 - alpha * m;
         c64 xn;
         if (mode == 0) {
@@ -593,7 +594,7 @@ enum { R64_FIRST = 0, R64_MID = 1, R64_LAST = 2 };
 // dynamic LDS as in col64_kernel
 template <int MODE, bool TWL>
 __global__ __launch_bounds__(F64_THREADS) void row64_kernel(c64* work, const c64* tw_g, Fft64 pl, int n1, int LN, int tw_lds, const void* x, int dtype, const double* mask,
-                                                            void* out, double* partial, int adaptive, int write_out, double alpha, const int* done, int zero_fill)
+                                                            size_t mask_stride, void* out, double* partial, int adaptive, int write_out, double alpha, const int* done, int zero_fill)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ double red[F64_THREADS / 64];
@@ -644,7 +645,7 @@ __global__ __launch_bounds__(F64_THREADS) void row64_kernel(c64* work, const c64
             else if (dtype == P3D_F64) xo = c64{reinterpret_cast<const double*>(x)[g], 0.0};
             else if (dtype == P3D_C64) { const float2 t = reinterpret_cast<const float2*>(x)[g]; xo = c64{(double)t.x, (double)t.y}; }
             else xo = c64{(double)reinterpret_cast<const float*>(x)[g], 0.0};
-            const double m = mask ? mask[li] : 0.0;
+            const double m = mask ? mask[(size_t)s * mask_stride + li] : 0.0;
             const double wgt = 1.0 - alpha * m;
             c64 xn;
             if (MODE == R64_FIRST) {
@@ -687,6 +688,7 @@ struct p3d_plan64 {
     c64 *tw_col = nullptr, *tw_row = nullptr, *work = nullptr, *tau = nullptr;
     void *st_x = nullptr, *st_out = nullptr;
     double *mask = nullptr, *partial = nullptr, *sums = nullptr, *spart = nullptr;
+    size_t mask_cap = 0, mask_stride = 0;   // elements of `mask` (one slice until the first P3D_FLAG_MASK_PER_SLICE job); the stride of the job in progress
     int* done = nullptr;
     size_t tau_cap = 0, sums_cap = 0;
     static constexpr int BLOCKS = 64;
@@ -780,7 +782,7 @@ int row_pass64(p3d_plan64* p, int dtype, double* sums_row, int adaptive, int wri
     if (p->mrow) {
         p3d::mix64::RowArgs64 a{};
         a.work = reinterpret_cast<p3d::mix::c64d*>(p->work); a.tab = reinterpret_cast<const p3d::mix::c64d*>(p->tw_mrow);
-        a.n1 = p->nil; a.nslices = nslices; a.x = p->cur_x; a.dtype = dtype; a.mask = (MODE == R64_FIRST && !adaptive) ? nullptr : p->mask; a.out = p->cur_out;
+        a.n1 = p->nil; a.nslices = nslices; a.x = p->cur_x; a.dtype = dtype; a.mask = (MODE == R64_FIRST && !adaptive) ? nullptr : p->mask; a.mask_stride = p->mask_stride; a.out = p->cur_out;
         a.partial = p->spart; a.adaptive = adaptive; a.write_out = write_out; a.alpha = alpha; a.done = done; a.zero_fill = zero_fill;
         a.nzflag = (MODE != R64_FIRST && p->sparse) ? p->nzflag : nullptr; a.nz_tiles = p->tiles_col(); a.nz_col_t = p->ln_col;
         P3D_TRY(p->mrow->row(MODE, a, p->stream));
@@ -791,7 +793,7 @@ int row_pass64(p3d_plan64* p, int dtype, double* sums_row, int adaptive, int wri
     auto kern = p->tw_row_lds ? row64_kernel<MODE, true> : row64_kernel<MODE, false>;
     if (p->lds_row > 64 * 1024) P3D_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_row));
     kern<<<dim3(p->tiles_row(), nslices), p->thr_row, p->lds_row, p->stream>>>(p->work, p->tw_row, p->frow, p->nil, p->ln_row, p->tw_row_lds, p->cur_x, dtype,
-                                                                              (MODE == R64_FIRST && !adaptive) ? nullptr : p->mask, p->cur_out, p->spart, adaptive, write_out, alpha,
+                                                                              (MODE == R64_FIRST && !adaptive) ? nullptr : p->mask, p->mask_stride, p->cur_out, p->spart, adaptive, write_out, alpha,
                                                                               done, zero_fill);
     fold64_kernel<<<nslices, 64, 0, p->stream>>>(p->spart, sums_row, nslices, p->tiles_row());
     P3D_TRY(hipGetLastError());
@@ -809,7 +811,7 @@ int check64(p3d_plan64* p, int nslices, int dtype)
 
 int update(p3d_plan64* p, int dtype, double* sums_row, int mode, int adaptive, int write_out, double alpha, int nslices, const int* done, int zero_fill)
 {
-    update64_kernel<<<dim3(p3d_plan64::BLOCKS, nslices), 256, 0, p->stream>>>(p->work, p->cur_x, dtype, mode == 0 && !adaptive ? nullptr : p->mask, p->cur_out, p->spart, mode,
+    update64_kernel<<<dim3(p3d_plan64::BLOCKS, nslices), 256, 0, p->stream>>>(p->work, p->cur_x, dtype, mode == 0 && !adaptive ? nullptr : p->mask, p->mask_stride, p->cur_out, p->spart, mode,
                                                                               adaptive, write_out, alpha, p->per(), done, zero_fill);
     fold64_kernel<<<nslices, 64, 0, p->stream>>>(p->spart, sums_row, nslices, p3d_plan64::BLOCKS);
     P3D_TRY(hipGetLastError());
@@ -910,6 +912,7 @@ static int create64(p3d_plan64** out, int device, int nil, int nxl, int max_slic
         ALLOC64(p->st_out, sizeof(c64) * per * S);
     }
     ALLOC64(p->mask, sizeof(double) * per);
+    p->mask_cap = per;
     ALLOC64(p->partial, sizeof(double) * 8 * nparts * S);
     ALLOC64(p->spart, sizeof(double) * nparts * S);
     ALLOC64(p->done, sizeof(int) * S);
@@ -980,7 +983,7 @@ int p3d_pocs64_run(p3d_plan64* p, const void* x, int dtype, const double* mask, 
     const size_t cube_bytes = elem_bytes(dtype) * per * nslices;
     if ((rc = take_x(p, x, cube_bytes))) return rc;
     const bool direct_out = choose_out(p, x, out, cube_bytes);
-    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * per, hipMemcpyDefault, p->stream));
+    if ((rc = stage_mask(p->mask, p->mask_cap, mask, per, prm, nslices, p->max_slices, p->stream, &p->mask_stride))) return rc;
     P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));   // (Re, Im) pairs of doubles: c64's layout
     if ((rc = frame.begin())) return rc;
     p->sparse = p->nzflag != nullptr;   // (tiles of the spectrum that the threshold empties are neither transformed back, stored nor read again: exact)
@@ -1042,6 +1045,7 @@ int p3d_fft2_c128(p3d_plan64* p, const void* in_host, void* out_host, int nslice
         if (p->fused) {
             P3D_TRY(hipMemsetAsync(p->st_x, 0, bytes, p->stream));
             P3D_TRY(hipMemsetAsync(p->mask, 0, sizeof(double) * p->per(), p->stream));
+            p->mask_stride = 0;
             p->cur_x = p->st_x;
             p->cur_out = p->st_out;
             if (p->mcol) rc = p3d::plan64_shear_cols(p, nullptr, nullptr, nslices, 1, 0, 0, 0, 0, 1, 1.0 / p->nil, nullptr, nullptr, 0);
@@ -1072,7 +1076,10 @@ bool plan64_engine_shape(int nil, int nxl)
 {
     return nil >= 1 && nxl >= 1 && nil <= F64_MAX_N && nxl <= F64_MAX_N && !getenv("P3D_F64_UNFUSED") && p3d::mix64::find(nil) != nullptr && p3d::mix64::find(nxl) != nullptr;
 }
-double* plan64_mask(p3d_plan64* p) { return p->mask; }
+int plan64_take_mask(p3d_plan64* p, const double* mask, const p3d_pocs_params* prm, int nslices)
+{
+    return stage_mask(p->mask, p->mask_cap, mask, p->per(), prm, nslices, p->max_slices, p->stream, &p->mask_stride);
+}
 void* plan64_stage_x(p3d_plan64* p) { return p->st_x; }
 void* plan64_stage_out(p3d_plan64* p) { return p->st_out; }
 void plan64_bind(p3d_plan64* p, const void* x, void* out)

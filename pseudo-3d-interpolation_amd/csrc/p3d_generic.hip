@@ -127,7 +127,8 @@ __device__ inline double block_sum(double v, double* sh)
 
 // mode 0: first input  (w = x or its APOCS mix, sums[0] += |x|)
 // mode 1: re-insertion (xn = w*(1-alpha*m) + alpha*x; sums += |xn|; optional out = xn; w = xn or its APOCS mix)
-__global__ void gen_update_kernel(c32* w, const void* x, int dtype, const float* mask, void* out, double* sums, int mode,
+// mask_stride: elements between the masks of consecutive slices, 0 for one mask shared by the batch (P3D_FLAG_MASK_PER_SLICE: per_slice)
+__global__ void gen_update_kernel(c32* w, const void* x, int dtype, const float* mask, size_t mask_stride, void* out, double* sums, int mode,
                                   int adaptive, int write_out, float alpha, size_t per_slice, const int* done, int zero_fill)
 {
     __shared__ double sh[256];
@@ -147,7 +148,7 @@ __global__ void gen_update_kernel(c32* w, const void* x, int dtype, const float*
         c32 xo;
         if (dtype == 0) xo = reinterpret_cast<const c32*>(x)[g];
         else xo = c32{reinterpret_cast<const float*>(x)[g], 0.f};
-        const float m = mask ? mask[i] : 0.f;
+        const float m = mask ? mask[(size_t)s * mask_stride + i] : 0.f;
         const float wgt = 1.0f - alpha * m;
         c32 xn;
         if (mode == 0) {
@@ -405,11 +406,11 @@ hipError_t gen_launch_shrink(c32* w, const c32* tau, int niter, int iter, int op
     return hipGetLastError();
 }
 
-hipError_t gen_launch_update(c32* w, const void* x, int dtype, const float* mask, void* out, double* sums, int mode, int adaptive,
+hipError_t gen_launch_update(c32* w, const void* x, int dtype, const float* mask, size_t mask_stride, void* out, double* sums, int mode, int adaptive,
                              int write_out, float alpha, int nslices, size_t per_slice, const int* done, int zero_fill, hipStream_t st)
 {
     const unsigned bx = (unsigned)((per_slice + 255) / 256 < 256 ? (per_slice + 255) / 256 : 256);
-    gen_update_kernel<<<dim3(bx, nslices), 256, 0, st>>>(w, x, dtype, mask, out, sums, mode, adaptive, write_out, alpha, per_slice, done,
+    gen_update_kernel<<<dim3(bx, nslices), 256, 0, st>>>(w, x, dtype, mask, mask_stride, out, sums, mode, adaptive, write_out, alpha, per_slice, done,
                                                        zero_fill);
     return hipGetLastError();
 }

@@ -25,7 +25,8 @@ hipError_t gen_launch_line_fft(const c32* in, c32* out, const c32* tw, const Gen
                                int n1, int n2, bool rows, const int* done, hipStream_t st);
 hipError_t gen_launch_shrink(c32* w, const c32* tau, int niter, int iter, int op, int nslices, size_t per_slice, const int* done,
                              hipStream_t st);
-hipError_t gen_launch_update(c32* w, const void* x, int dtype, const float* mask, void* out, double* sums, int mode, int adaptive,
+// mask_stride: elements between the masks of consecutive slices, 0 for one mask shared by the batch
+hipError_t gen_launch_update(c32* w, const void* x, int dtype, const float* mask, size_t mask_stride, void* out, double* sums, int mode, int adaptive,
                              int write_out, float alpha, int nslices, size_t per_slice, const int* done, int zero_fill, hipStream_t st);
 hipError_t gen_launch_stats(const c32* w, float* partial, int nslices, size_t per_slice, int blocks, hipStream_t st);
 

@@ -63,6 +63,18 @@ int grow(T*& ptr, size_t& cap, size_t n)
     return P3D_OK;
 }
 
+// The mask of a job into a plan's own buffer, on the plan's stream (`mask` may be a host or a device pointer).  The buffer holds one slice
+// until the first P3D_FLAG_MASK_PER_SLICE job, then max_slices slices; *stride is what the update kernels add per slice (0: shared mask).
+template <class T>
+int stage_mask(T*& buf, size_t& cap, const T* mask, size_t per, const p3d_pocs_params* prm, int nslices, int max_slices, hipStream_t stream, size_t* stride)
+{
+    const bool per_slice = (prm->flags & P3D_FLAG_MASK_PER_SLICE) != 0;
+    if (int rc = grow(buf, cap, per * (per_slice ? (size_t)max_slices : 1))) return rc;
+    P3D_TRY(hipMemcpyAsync(buf, mask, sizeof(T) * per * (per_slice ? (size_t)nslices : 1), hipMemcpyDefault, stream));
+    *stride = per_slice ? per : 0;
+    return P3D_OK;
+}
+
 // the per-slice state of a loop: 0 = running, -1 = switched off by the caller (`active`, NULL: every slice runs), k > 0 = converged at iteration k
 inline std::vector<int> done_from_active(const uint8_t* active, int nslices)
 {

@@ -75,7 +75,8 @@ int plan64_fft2(p3d_plan64* plan, void* buf, int nslices, bool inverse, const in
 // the plan's work buffer holds the slices' spectra F, U is the caller's coefficient buffer [nb * nsh][nil][nxl] complex128, psi [nsh][nil][nxl] doubles
 bool plan64_shear_supported(p3d_plan64* plan);
 bool plan64_engine_shape(int nil, int nxl);   // both extents have a plan on the register engine (what plan64_shear_supported will find for such a plan)
-double* plan64_mask(p3d_plan64* plan);      // device [nil][nxl]: the caller fills it
+// the mask of the job about to run (host or device doubles, [nil][nxl] or with P3D_FLAG_MASK_PER_SLICE [nslices][nil][nxl]) into the plan's own buffer, on its stream
+int plan64_take_mask(p3d_plan64* plan, const double* mask, const p3d_pocs_params* prm, int nslices);
 void* plan64_stage_x(p3d_plan64* plan);     // staging buffers for host cubes (max_slices slices of complex128)
 void* plan64_stage_out(p3d_plan64* plan);
 void plan64_bind(p3d_plan64* plan, const void* x, void* out);   // device pointers of the observed cube and the result the row passes read / write

@@ -227,7 +227,9 @@ __global__ __launch_bounds__(PL::ROWLB* PL::TMAX) void row_kernel(const RowArgs6
     double acc = 0.0;
     const double inv = 1.0 / N;
     const int i0 = tl < TPL_A ? tl : 0;
-    const double* const mrow = a.mask ? a.mask + rbase : nullptr;
+    // mask[s * mask_stride + rbase + i]: the stride is 0 (one mask for the batch) or the cube's own slice stride, for which that offset is g0 -- formed from
+    // the two offsets at hand, the product costs several plans a register class (280-, 300-, 360-point rows: 128 -> 136)
+    const double* const mrow = a.mask ? a.mask + (a.mask_stride ? g0 : rbase) : nullptr;
 #pragma unroll
     for (int q = 0; q < PPT_A; ++q) {
         const int i = i0 + TPL_A * q;

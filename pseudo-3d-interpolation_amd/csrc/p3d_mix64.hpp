@@ -27,6 +27,8 @@ struct RowArgs64 {
     const void* x;
     int dtype;                 // P3D_C128 / P3D_F64 / P3D_C64 / P3D_F32 (of x and out)
     const double* mask;
+    size_t mask_stride;        // 0 (one mask shared by the batch) or EXACTLY n1 * N (one mask per slice, laid out like the cube): the kernel only asks whether it
+                               //   is zero and then uses the cube's own slice offset -- any other value (a padded stride) is not honoured
     void* out;
     double* partial;
     int adaptive, write_out;

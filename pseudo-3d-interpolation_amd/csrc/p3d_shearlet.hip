@@ -28,6 +28,7 @@ using p3d::c32;
 using p3d::fail;
 using p3d::grow;
 using p3d::LoopFrame;
+using p3d::stage_mask;
 
 namespace {
 
@@ -160,7 +161,7 @@ __global__ void sstats_kernel(const c32* U, size_t per, int real_only, float* st
 
 // mode 0: first input (feed = x or its APOCS mix; sums += |x|)
 // mode 1: re-insertion (POCS.py:616-619) of A = ifft2(...), sums += |x_new|, feed for the next iteration
-__global__ void supdate_kernel(const c32* A, c32* feed, const void* x, int dtype, const float* mask, void* out, double* sums, int mode, int adaptive,
+__global__ void supdate_kernel(const c32* A, c32* feed, const void* x, int dtype, const float* mask, size_t mask_stride, void* out, double* sums, int mode, int adaptive,
                                int write_out, float alpha, size_t per, const int* done, int zero_fill)
 {
     __shared__ double sh[256];
@@ -177,7 +178,7 @@ __global__ void supdate_kernel(const c32* A, c32* feed, const void* x, int dtype
         for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < per; i += (size_t)gridDim.x * blockDim.x) {
             const size_t g = (size_t)b * per + i;
             const c32 xo = real_only ? c32{reinterpret_cast<const float*>(x)[g], 0.f} : reinterpret_cast<const c32*>(x)[g];
-            const float m = mask ? mask[i] : 0.f;
+            const float m = mask ? mask[(size_t)b * mask_stride + i] : 0.f;
             const float wgt = 1.0f - alpha * m;
             c32 xn;
             if (mode == 0) {
@@ -235,6 +236,7 @@ struct p3d_splan {
     double* sums = nullptr;
     int* done = nullptr;
     float *stats = nullptr, *mask = nullptr;
+    size_t mask_cap = 0;   // elements of `mask`: one slice until the first P3D_FLAG_MASK_PER_SLICE job
     void *st_x = nullptr, *st_out = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     size_t per() const { return (size_t)nil * nxl; }
@@ -282,6 +284,7 @@ extern "C" int p3d_shearlet_plan_create(p3d_splan** out, int device, int nil, in
     ALLOC(p->done, sizeof(int) * S);
     ALLOC(p->stats, sizeof(float) * 5 * nsh * S);
     ALLOC(p->mask, sizeof(float) * per);
+    p->mask_cap = per;
     ALLOC(p->st_x, sizeof(c32) * per * S);
     ALLOC(p->st_out, sizeof(c32) * per * S);
 #undef ALLOC
@@ -398,7 +401,7 @@ int p3d_shearlet_stats(p3d_splan* p, const void* x, int dtype, int nslices, doub
     P3D_TRY(hipMemcpyAsync(p->st_x, x, esz * p->per() * nslices, hipMemcpyDefault, p->stream));
     if (p->sums_cap < (size_t)nslices) S_RC(grow(p->sums, p->sums_cap, 2 * (size_t)p->max_slices));
     P3D_TRY(hipMemsetAsync(p->sums, 0, sizeof(double) * nslices, p->stream));
-    supdate_kernel<<<dim3(blocks_for(p->per(), 256), nslices), 256, 0, p->stream>>>(nullptr, p->feed, p->st_x, dtype, nullptr, nullptr, p->sums, 0, 0, 0, 1.0f,
+    supdate_kernel<<<dim3(blocks_for(p->per(), 256), nslices), 256, 0, p->stream>>>(nullptr, p->feed, p->st_x, dtype, nullptr, 0, nullptr, p->sums, 0, 0, 0, 1.0f,
                                                                                   p->per(), nullptr, 0);
     std::vector<float> host((size_t)nslices * p->nsh * 5);
     if (p->pair && dtype == P3D_F32) {
@@ -440,11 +443,12 @@ int p3d_shearlet_run(p3d_splan* p, const void* x, int dtype, const float* mask, 
     }
     LoopFrame frame(p, active, nslices, niter);
     P3D_TRY(hipMemcpyAsync(p->st_x, x, esz * per * nslices, hipMemcpyDefault, p->stream));   // x, mask, out: host or device pointers (on the plan's stream, see p3d_shearlet_stats)
-    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(float) * per, hipMemcpyDefault, p->stream));
+    size_t mask_stride = 0;
+    S_RC(stage_mask(p->mask, p->mask_cap, mask, per, prm, nslices, p->max_slices, p->stream, &mask_stride));
     P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
     S_RC(frame.begin());
     const dim3 ugrid(blocks_for(per, 256), nslices);
-    supdate_kernel<<<ugrid, 256, 0, p->stream>>>(nullptr, p->feed, p->st_x, dtype, p->mask, p->st_out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, per,
+    supdate_kernel<<<ugrid, 256, 0, p->stream>>>(nullptr, p->feed, p->st_x, dtype, p->mask, mask_stride, p->st_out, p->sums, 0, adaptive ? 1 : 0, 0, (float)prm->alpha, per,
                                                 p->done, 0);
     for (int k = 0; k < niter; ++k) {
         const bool last = k + 1 == niter;
@@ -464,7 +468,7 @@ int p3d_shearlet_run(p3d_splan* p, const void* x, int dtype, const float* mask, 
                                                                                           real_only ? 1 : 0, p->done);
             S_RC(s_inverse(p, nslices, p->done));
         }
-        supdate_kernel<<<ugrid, 256, 0, p->stream>>>(p->F, p->feed, p->st_x, dtype, p->mask, p->st_out, p->sums + (size_t)(k + 1) * nslices, 1,
+        supdate_kernel<<<ugrid, 256, 0, p->stream>>>(p->F, p->feed, p->st_x, dtype, p->mask, mask_stride, p->st_out, p->sums + (size_t)(k + 1) * nslices, 1,
                                                     (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0, (float)prm->alpha, per, p->done, last ? 1 : 0);
         if (early) sconv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
     }

@@ -32,6 +32,7 @@ using p3d::fail;
 using p3d::elem_bytes;
 using p3d::grow;
 using p3d::LoopFrame;
+using p3d::stage_mask;
 using p3d::on_plan_device;
 using p3d::real_dtype;
 using p3d::take_x;
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(256) void sstats64_kernel(const c64* U, size_t per,
 // One workgroup per row, IN PLACE on F (A = ifft2(...) on entry, the next iteration's input on exit).
 // mode 0: first input (F = x or its APOCS mix; rowsum = sum |x| per row)
 // mode 1: re-insertion (POCS.py:616-619), rowsum = sum |x_new| per row, F = the next input (POCS.py:572-575)
-__global__ __launch_bounds__(256) void supdate64_kernel(c64* F, const void* x, int dtype, const double* mask, void* out, double* rowsum, int mode, int adaptive,
+__global__ __launch_bounds__(256) void supdate64_kernel(c64* F, const void* x, int dtype, const double* mask, size_t mask_stride, void* out, double* rowsum, int mode, int adaptive,
                                                         int write_out, double alpha, int n1, int n2, const int* done, int zero_fill, int real_only)
 {
     __shared__ double sh[256];
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256) void supdate64_kernel(c64* F, const void* x, i
         if (threadIdx.x == 0) rowsum[(size_t)b * n1 + r] = 0.0;
         return;
     }
-    const double* const mrow = mask ? mask + (size_t)r * n2 : nullptr;
+    const double* const mrow = mask ? mask + (size_t)b * mask_stride + (size_t)r * n2 : nullptr;
     double acc = 0.0;
     for (int c = threadIdx.x; c < n2; c += blockDim.x) {
         const size_t g = g0 + c;
@@ -307,7 +308,7 @@ struct p3d_splan64 {
     bool pair = false;           // fused form, REAL cubes: Hermitian coefficient slices (rows 0 ... nil/2 only), two columns per transform (symmetric spectra, nil and nxl even;
                                  // P3D_SHEARLET64_NO_PAIR=1 switches it off)
     c64 *U = nullptr, *F = nullptr, *tau = nullptr;
-    size_t tau_cap = 0, sums_cap = 0;
+    size_t tau_cap = 0, sums_cap = 0, mask_cap = 0;   // (mask: the unfused form's own buffer -- the fused form's is the slice plan's, plan64_take_mask)
     double *sums = nullptr, *rowsum = nullptr, *stats = nullptr, *mask = nullptr;
     int* done = nullptr;
     void *st_x = nullptr, *st_out = nullptr;
@@ -413,13 +414,13 @@ int p3d_shearlet64_plan_create(p3d_splan64** out, int device, int nil, int nxl, 
     ALLOC(p->stats, sizeof(double) * 5 * nsh * S);
     if (p->pf) {
         ALLOC(p->U, sizeof(c64) * per * nsh * S);
-        p->mask = p3d::plan64_mask(p->pf);
         p->st_x = p3d::plan64_stage_x(p->pf);
         p->st_out = p3d::plan64_stage_out(p->pf);
     } else {
         ALLOC(p->F, sizeof(c64) * per * S);
         ALLOC(p->rowsum, sizeof(double) * nil * S);
         ALLOC(p->mask, sizeof(double) * per);
+        p->mask_cap = per;
         ALLOC(p->st_x, sizeof(c64) * per * S);
         ALLOC(p->st_out, sizeof(c64) * per * S);
     }
@@ -492,7 +493,7 @@ int p3d_shearlet64_stats(p3d_splan64* p, const void* x, int dtype, int nslices, 
         S_RC(p3d::plan64_shear_spread(p->pf, p->psi, p->U, nslices, p->nsh, nullptr, p->sup, pair ? p->nil / 2 + 1 : 0));
         S_RC(p3d::plan64_shear_cols(p->pf, p->U, nullptr, nslices, p->nsh, 0, 0, 0, 0, 1, 1.0 / ((double)p->nil * p->nxl), nullptr, p->sup, pair));
     } else {
-        supdate64_kernel<<<dim3(p->nil, nslices), 256, 0, p->stream>>>(p->F, p->cur_x, dtype, nullptr, nullptr, p->rowsum, 0, 0, 0, 1.0, p->nil, p->nxl, nullptr, 0, 0);
+        supdate64_kernel<<<dim3(p->nil, nslices), 256, 0, p->stream>>>(p->F, p->cur_x, dtype, nullptr, 0, nullptr, p->rowsum, 0, 0, 0, 1.0, p->nil, p->nxl, nullptr, 0, 0);
         S_RC(s_forward(p, nslices, nullptr));
     }
     sstats64_kernel<<<nslices * p->nsh, 256, 0, p->stream>>>(p->U, p->per(), real_dtype(dtype) ? 1 : 0, p->stats);
@@ -525,7 +526,9 @@ int p3d_shearlet64_run(p3d_splan64* p, const void* x, int dtype, const double* m
     S_RC(take_x(p, x, elem_bytes(dtype) * per * nslices));
     const bool direct_out = on_plan_device(p, out);   // (no overlap test here, unlike choose_out)
     p->cur_out = direct_out ? out : p->st_out;
-    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * per, hipMemcpyDefault, p->stream));
+    size_t mask_stride = 0;
+    if (p->pf) S_RC(p3d::plan64_take_mask(p->pf, mask, prm, nslices));
+    else S_RC(stage_mask(p->mask, p->mask_cap, mask, per, prm, nslices, p->max_slices, p->stream, &mask_stride));
     P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));
     S_RC(frame.begin());
     if (p->pf) {
@@ -546,7 +549,7 @@ int p3d_shearlet64_run(p3d_splan64* p, const void* x, int dtype, const double* m
         }
     } else {
         const dim3 ugrid(p->nil, nslices);
-        supdate64_kernel<<<ugrid, 256, 0, p->stream>>>(p->F, p->cur_x, dtype, p->mask, p->cur_out, p->rowsum, 0, adaptive ? 1 : 0, 0, prm->alpha, p->nil, p->nxl, p->done, 0,
+        supdate64_kernel<<<ugrid, 256, 0, p->stream>>>(p->F, p->cur_x, dtype, p->mask, mask_stride, p->cur_out, p->rowsum, 0, adaptive ? 1 : 0, 0, prm->alpha, p->nil, p->nxl, p->done, 0,
                                                       real_only ? 1 : 0);
         srowsum64_kernel<<<nslices, 256, 0, p->stream>>>(p->rowsum, p->sums, p->nil, p->done);
         for (int k = 0; k < niter; ++k) {
@@ -555,7 +558,7 @@ int p3d_shearlet64_run(p3d_splan64* p, const void* x, int dtype, const double* m
             sthreshold64_kernel<<<dim3(blocks_for(per, 64), nslices * nsh), 256, 0, p->stream>>>(p->U, per, nsh, p->tau, niter, k, prm->thresh_op, real_only ? 1 : 0, p->done);
             S_RC(s_inverse(p, nslices, p->done));
             // (early exit: every iterate is stored, so that a slice that converges keeps its last one -- sconv64_kernel switches it off afterwards)
-            supdate64_kernel<<<ugrid, 256, 0, p->stream>>>(p->F, p->cur_x, dtype, p->mask, p->cur_out, p->rowsum, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0,
+            supdate64_kernel<<<ugrid, 256, 0, p->stream>>>(p->F, p->cur_x, dtype, p->mask, mask_stride, p->cur_out, p->rowsum, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0,
                                                           prm->alpha, p->nil, p->nxl, p->done, last ? 1 : 0, real_only ? 1 : 0);
             srowsum64_kernel<<<nslices, 256, 0, p->stream>>>(p->rowsum, p->sums + (size_t)(k + 1) * nslices, p->nil, p->done);
             if (early) sconv64_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);

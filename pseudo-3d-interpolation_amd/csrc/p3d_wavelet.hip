@@ -34,6 +34,7 @@ using p3d::choose_out;
 using p3d::elem_bytes;
 using p3d::grow;
 using p3d::LoopFrame;
+using p3d::stage_mask;
 using p3d::take_x;
 using p3d::c32;
 
@@ -598,6 +599,7 @@ struct Update {
     const void* x;      // observed slices (dtype)
     int dtype;
     const float* mask;
+    size_t mask_stride;          // elements between the masks of consecutive slices (0: one mask shared by the batch)
     const unsigned* mask_bits;   // the same as one bit per sample, rows of mask_words words -- NULL unless every weight is 0 or 1 (wfuse1_kernel)
     int mask_words;
     void* out;
@@ -811,7 +813,7 @@ __global__ __launch_bounds__((WTILE_NT<T, TILE>)) void idwt2_tile_kernel(const T
                 if (m < u.n1 && n + e < u.n2) {
                     const size_t li = (size_t)m * u.n2 + n + e;
                     xo[i][e] = load_x(u.x, u.dtype, (size_t)s * per + li, (T*)nullptr);
-                    mk[i][e] = u.mask[li];
+                    mk[i][e] = u.mask[(size_t)s * u.mask_stride + li];
                 }
             }
         }
@@ -971,7 +973,7 @@ __global__ __launch_bounds__(WFUSE1_NT<T>) void wfuse1_kernel(const T* a, size_t
                     if (e < IHc * (IHc / 2) && m < nm && gn <= n_hi) {
                         const unsigned li = (unsigned)gm * (unsigned)u.n2 + (unsigned)gn;
                         xo[it][ee] = load_xs(xs, u.dtype, li, (T*)nullptr);
-                        if constexpr (!MBITS) mk[it][ee] = u.mask[li];
+                        if constexpr (!MBITS) mk[it][ee] = u.mask[(size_t)s * u.mask_stride + li];
                     }
                 }
             }
@@ -1083,7 +1085,7 @@ __global__ __launch_bounds__(WFUSE1_NT<T>) void wfuse1_kernel(const T* a, size_t
                     if (gn <= n_hi) {
                         const size_t li = (size_t)(m_lo + m) * u.n2 + gn;
                         x2[ee] = load_x(u.x, u.dtype, (size_t)s * per + li, (T*)nullptr);
-                        m2[ee] = u.mask[li];
+                        m2[ee] = u.mask[(size_t)s * u.mask_stride + li];
                     }
                 }
                 sample(m, ii, x2, m2);
@@ -1230,7 +1232,7 @@ __global__ void wstats_kernel(const T* coef, size_t coef_slice, const WStatLevel
 // mode 1: crop of the reconstruction + re-insertion (POCS.py:609, 616-619), sums += |x_new|, feed for the next iteration
 // T = element type of the work buffers (float requires dtype == P3D_F32)
 template <typename T>
-__global__ void wupdate_kernel(const T* rec, size_t rec_ld, size_t rec_slice, T* feed, const void* x, int dtype, const float* mask, void* out, double* sums,
+__global__ void wupdate_kernel(const T* rec, size_t rec_ld, size_t rec_slice, T* feed, const void* x, int dtype, const float* mask, size_t mask_stride, void* out, double* sums,
                                int mode, int adaptive, int write_out, float alpha, int n1, int n2, const int* done, int zero_fill)
 {
     __shared__ double sh[256];
@@ -1246,7 +1248,7 @@ __global__ void wupdate_kernel(const T* rec, size_t rec_ld, size_t rec_slice, T*
         for (int r = blockIdx.x; r < n1; r += gridDim.x) {
             const size_t g0 = (size_t)s * per + (size_t)r * n2;
             const T* const rrow = rec ? rec + (size_t)s * rec_slice + (size_t)r * rec_ld : nullptr;
-            const float* const mrow = mask ? mask + (size_t)r * n2 : nullptr;
+            const float* const mrow = mask ? mask + (size_t)s * mask_stride + (size_t)r * n2 : nullptr;
             float racc = 0.f;
             for (int c = threadIdx.x; c < n2; c += blockDim.x) {
                 const size_t g = g0 + c;
@@ -1310,6 +1312,7 @@ struct p3d_wplan {
     float *stats = nullptr, *mask = nullptr;
     unsigned* mask_bits = nullptr;   // one bit per sample of the mask, rows of mask_words words, + one int behind them: 1 = every weight is 0 or 1
     int mask_words = 0, mask_binary = 0;
+    size_t mask_cap = 0, mask_stride = 0;   // elements of `mask`; the stride of the job in progress (P3D_FLAG_MASK_PER_SLICE: per(), else 0)
     void *st_x = nullptr, *st_out = nullptr;
     // the observed cube and the result of the job in progress: the caller's own device buffers where it passed such (no staging
     // copies: 0.4 ms each way per 256 MiB), the staging buffers above otherwise
@@ -1434,6 +1437,7 @@ extern "C" int p3d_wavelet_plan_create(p3d_wplan** out, int device, int nil, int
     ALLOC(p->done, sizeof(int) * S);
     ALLOC(p->stats, sizeof(float) * 4 * 3 * (size_t)level * S);
     ALLOC(p->mask, sizeof(float) * p->per());
+    p->mask_cap = p->per();
     p->mask_words = (nxl + 31) / 32;
     ALLOC(p->mask_bits, sizeof(unsigned) * ((size_t)nil * p->mask_words + 1));
     ALLOC(p->st_x, sizeof(c32) * p->per() * S);
@@ -1677,7 +1681,7 @@ static int w_check(p3d_wplan* p, int nslices, int dtype)
 template <typename T>
 static int w_stats(p3d_wplan* p, int dtype, int nslices)
 {
-    wupdate_kernel<T><<<dim3(p->nil < 256 ? p->nil : 256, nslices), 256, 0, p->stream>>>(nullptr, 0, 0, as<T>(p->feed), p->cur_x, dtype, nullptr, nullptr, p->sums, 0, 0, 0, 1.0f,
+    wupdate_kernel<T><<<dim3(p->nil < 256 ? p->nil : 256, nslices), 256, 0, p->stream>>>(nullptr, 0, 0, as<T>(p->feed), p->cur_x, dtype, nullptr, 0, nullptr, p->sums, 0, 0, 0, 1.0f,
                                                                                 p->nil, p->nxl, nullptr, 0);
     int rc = w_forward<T>(p, nslices, nullptr);
     if (rc) return rc;
@@ -1699,7 +1703,7 @@ static int w_loop(p3d_wplan* p, int dtype, int nslices, const p3d_pocs_params* p
     struct LoopDone { p3d_wplan* p; ~LoopDone() { p->loop_done = nullptr; } } loop_done_guard{p};
     p->loop_done = (early && p->fused) ? p->done : nullptr;
     const dim3 ugrid(p->nil < 256 ? p->nil : 256, nslices);   // (a block walks over rows)
-    wupdate_kernel<T><<<ugrid, 256, 0, p->stream>>>(nullptr, 0, 0, as<T>(p->feed), p->cur_x, dtype, p->mask, p->cur_out, p->sums, 0, adaptive ? 1 : 0, 0,
+    wupdate_kernel<T><<<ugrid, 256, 0, p->stream>>>(nullptr, 0, 0, as<T>(p->feed), p->cur_x, dtype, p->mask, p->mask_stride, p->cur_out, p->sums, 0, adaptive ? 1 : 0, 0,
                                                    (float)prm->alpha, p->nil, p->nxl, p->done, 0);
     const bool l1fuse = p->fused && (sizeof(T) == sizeof(float) ? p->l1fuse_r : p->l1fuse_c);
     // level-1 details of iteration k live in buffer k % 2 (the level-1 kernel reads one while it writes the other)
@@ -1718,7 +1722,7 @@ static int w_loop(p3d_wplan* p, int dtype, int nslices, const p3d_pocs_params* p
         if (rc) return rc;
         if (p->fused) {
             Update u{};
-            u.enabled = 1; u.feed = p->feed; u.x = p->cur_x; u.dtype = dtype; u.mask = p->mask; u.out = p->cur_out;
+            u.enabled = 1; u.feed = p->feed; u.x = p->cur_x; u.dtype = dtype; u.mask = p->mask; u.mask_stride = p->mask_stride; u.out = p->cur_out;
             u.mask_bits = p->mask_binary ? p->mask_bits : nullptr; u.mask_words = p->mask_words;
             u.sums = p->sums + (size_t)(k + 1) * nslices;
             // (early exit: the iterate of a slice that converges is rebuilt once, after the loop, from the coefficients it stopped at -- storing every
@@ -1752,14 +1756,14 @@ static int w_loop(p3d_wplan* p, int dtype, int nslices, const p3d_pocs_params* p
         } else {
             if ((rc = w_inverse<T>(p, nslices))) return rc;
             wupdate_kernel<T><<<ugrid, 256, 0, p->stream>>>(as<T>(p->rec[0]), (size_t)p->rw[0], (size_t)p->rh[0] * p->rw[0], as<T>(p->feed), p->cur_x, dtype, p->mask,
-                                                           p->cur_out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0,
+                                                           p->mask_stride, p->cur_out, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0,
                                                            (float)prm->alpha, p->nil, p->nxl, p->done, last ? 1 : 0);
         }
         if (early) wconv_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
     }
     if (early && p->fused) {
         Update uf{};
-        uf.enabled = 1; uf.feed = p->feed; uf.x = p->cur_x; uf.dtype = dtype; uf.mask = p->mask; uf.out = p->cur_out;
+        uf.enabled = 1; uf.feed = p->feed; uf.x = p->cur_x; uf.dtype = dtype; uf.mask = p->mask; uf.mask_stride = p->mask_stride; uf.out = p->cur_out;
         uf.sums = p->sums;   // (not added to: the slices are finished)
         uf.write_out = 1; uf.alpha = (float)prm->alpha; uf.n1 = p->nil; uf.n2 = p->nxl; uf.done = p->done;
         uf.only_below = niter;
@@ -1849,9 +1853,10 @@ int p3d_wavelet_run(p3d_wplan* p, const void* x, int dtype, const float* mask, c
     const bool direct_out = choose_out(p, x, out, cube_bytes);
     // the mask may be a device pointer: a device-to-device hipMemcpy runs on the null stream, need not have finished when it returns, and the plan's
     // (non-blocking) stream does not wait for it -- every copy of this entry point goes onto the plan's stream
-    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(float) * p->per(), hipMemcpyDefault, p->stream));
+    if ((rc = stage_mask(p->mask, p->mask_cap, mask, p->per(), prm, nslices, p->max_slices, p->stream, &p->mask_stride))) return rc;
     p->mask_binary = 0;
-    if ((p->l1fuse_c || p->l1fuse_r) && !getenv("P3D_WAVELET_NO_MASK_BITS")) {   // wfuse1_kernel reads a 0 / 1 mask as bits
+    // wfuse1_kernel reads a 0 / 1 mask as bits (one shared mask only: a per-slice mask keeps its float weights)
+    if ((p->l1fuse_c || p->l1fuse_r) && !p->mask_stride && !getenv("P3D_WAVELET_NO_MASK_BITS")) {
         int* flag = reinterpret_cast<int*>(p->mask_bits + (size_t)p->nil * p->mask_words);
         const int one = 1, nw = p->nil * p->mask_words;
         P3D_TRY(hipMemcpyAsync(flag, &one, sizeof(int), hipMemcpyHostToDevice, p->stream));

@@ -29,6 +29,7 @@ using p3d::choose_out;
 using p3d::elem_bytes;
 using p3d::grow;
 using p3d::LoopFrame;
+using p3d::stage_mask;
 using p3d::real_dtype;
 using p3d::take_x;
 
@@ -259,7 +260,7 @@ __global__ void wstats64_kernel(const T* coef, size_t coef_slice, const WStatLev
 // One workgroup per row; the row sums are added up in a fixed order by wrowsum64_kernel (the cost, POCS.py:622, is a difference of two
 // nearly equal sums).
 template <typename T>
-__global__ __launch_bounds__(256) void wupdate64_kernel(const T* rec, size_t rec_ld, size_t rec_slice, T* feed, const void* x, int dtype, const double* mask, void* out,
+__global__ __launch_bounds__(256) void wupdate64_kernel(const T* rec, size_t rec_ld, size_t rec_slice, T* feed, const void* x, int dtype, const double* mask, size_t mask_stride, void* out,
                                                         double* rowsum, int mode, int adaptive, int write_out, double alpha, int n1, int n2, const int* done, int zero_fill)
 {
     __shared__ double sh[256];
@@ -273,7 +274,7 @@ __global__ __launch_bounds__(256) void wupdate64_kernel(const T* rec, size_t rec
         return;
     }
     const T* const rrow = rec ? rec + (size_t)s * rec_slice + (size_t)r * rec_ld : nullptr;
-    const double* const mrow = mask ? mask + (size_t)r * n2 : nullptr;
+    const double* const mrow = mask ? mask + (size_t)s * mask_stride + (size_t)r * n2 : nullptr;
     double acc = 0.0;
     for (int c = threadIdx.x; c < n2; c += blockDim.x) {
         const size_t g = g0 + c;
@@ -344,6 +345,7 @@ struct p3d_wplan64 {
     std::vector<c64*> approx, rec;
     double *sums = nullptr, *rowsum = nullptr, *stats = nullptr, *mask = nullptr;
     size_t sums_cap = 0, tau_cap = 0;
+    size_t mask_cap = 0, mask_stride = 0;   // elements of `mask` (one slice until the first P3D_FLAG_MASK_PER_SLICE job); the stride of the job in progress
     int* done = nullptr;
     void *st_x = nullptr, *st_out = nullptr;
     const void* cur_x = nullptr;
@@ -424,6 +426,7 @@ extern "C" int p3d_wavelet64_plan_create(p3d_wplan64** out, int device, int nil,
     ALLOC(p->stats, sizeof(double) * 4 * 3 * (size_t)level * S);
     ALLOC(p->rowsum, sizeof(double) * (size_t)nil * S);
     ALLOC(p->mask, sizeof(double) * p->per());
+    p->mask_cap = p->per();
     ALLOC(p->st_x, sizeof(c64) * p->per() * S);
     ALLOC(p->st_out, sizeof(c64) * p->per() * S);
 #undef ALLOC
@@ -515,7 +518,7 @@ static int w_check(p3d_wplan64* p, int nslices, int dtype)
 template <typename T>
 static int w_stats(p3d_wplan64* p, int dtype, int nslices)
 {
-    wupdate64_kernel<T><<<dim3(p->nil, nslices), 256, 0, p->stream>>>(nullptr, 0, 0, as<T>(p->feed), p->cur_x, dtype, nullptr, nullptr, p->rowsum, 0, 0, 0, 1.0, p->nil,
+    wupdate64_kernel<T><<<dim3(p->nil, nslices), 256, 0, p->stream>>>(nullptr, 0, 0, as<T>(p->feed), p->cur_x, dtype, nullptr, 0, nullptr, p->rowsum, 0, 0, 0, 1.0, p->nil,
                                                                     p->nxl, nullptr, 0);
     int rc = w_forward<T>(p, nslices, nullptr, nullptr);
     if (rc) return rc;
@@ -532,7 +535,7 @@ static int w_loop(p3d_wplan64* p, int dtype, int nslices, const p3d_pocs_params*
     const int niter = prm->niter;
     const bool early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE;
     const dim3 ugrid(p->nil, nslices);
-    wupdate64_kernel<T><<<ugrid, 256, 0, p->stream>>>(nullptr, 0, 0, as<T>(p->feed), p->cur_x, dtype, p->mask, p->cur_out, p->rowsum, 0, adaptive ? 1 : 0, 0, prm->alpha,
+    wupdate64_kernel<T><<<ugrid, 256, 0, p->stream>>>(nullptr, 0, 0, as<T>(p->feed), p->cur_x, dtype, p->mask, p->mask_stride, p->cur_out, p->rowsum, 0, adaptive ? 1 : 0, 0, prm->alpha,
                                                      p->nil, p->nxl, p->done, 0);
     wrowsum64_kernel<<<nslices, 256, 0, p->stream>>>(p->rowsum, p->sums, p->nil, p->done);
     for (int k = 0; k < niter; ++k) {
@@ -543,7 +546,7 @@ static int w_loop(p3d_wplan64* p, int dtype, int nslices, const p3d_pocs_params*
         if ((rc = w_inverse<T>(p, nslices, p->done))) return rc;
         // (early exit: every iterate is stored, so that a slice that converges keeps its last one -- wconv64_kernel switches it off afterwards)
         wupdate64_kernel<T><<<ugrid, 256, 0, p->stream>>>(as<T>(p->rec[0]), (size_t)p->rw[0], (size_t)p->rh[0] * p->rw[0], as<T>(p->feed), p->cur_x, dtype, p->mask,
-                                                         p->cur_out, p->rowsum, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0, prm->alpha, p->nil, p->nxl, p->done,
+                                                         p->mask_stride, p->cur_out, p->rowsum, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0, prm->alpha, p->nil, p->nxl, p->done,
                                                          last ? 1 : 0);
         wrowsum64_kernel<<<nslices, 256, 0, p->stream>>>(p->rowsum, p->sums + (size_t)(k + 1) * nslices, p->nil, p->done);
         if (early) wconv64_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
@@ -591,7 +594,7 @@ int p3d_wavelet64_run(p3d_wplan64* p, const void* x, int dtype, const double* ma
     if ((rc = take_x(p, x, cube_bytes))) return rc;
     const bool direct_out = choose_out(p, x, out, cube_bytes);
     // every copy goes onto the plan's (non-blocking) stream: a device-to-device hipMemcpy on the null stream need not have finished when it returns
-    P3D_TRY(hipMemcpyAsync(p->mask, mask, sizeof(double) * p->per(), hipMemcpyDefault, p->stream));
+    if ((rc = stage_mask(p->mask, p->mask_cap, mask, p->per(), prm, nslices, p->max_slices, p->stream, &p->mask_stride))) return rc;
     P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));
     if ((rc = frame.begin())) return rc;
     if ((rc = real_path ? w_loop<double>(p, dtype, nslices, prm) : w_loop<c64>(p, dtype, nslices, prm))) return rc;

@@ -110,12 +110,26 @@ def main(argv=sys.argv, return_dataset=False):
 
     cube = open_cube(path_cube)
     dim = cfg['dim']
-    var = cfg.get('var', [v for v in list(cube.data_vars) if v != 'fold'][0])
+    mask_var = cfg.get('mask_var')                           # optional (an extension): a variable of the cube used as the mask
+    var = cfg.get('var', [v for v in list(cube.data_vars) if v not in ('fold', mask_var)][0])
     fold = np.asarray(cube.data_vars['fold'])
     mask = np.where(fold <= 1, fold, 1)                      # cube_POCS_interpolation_3D.py:242-244
     data = np.asarray(cube.data_vars[var])
     if cube.dims[var][0] != dim:
         data = np.moveaxis(data, cube.dims[var].index(dim), 0)
+    if mask_var is not None:
+        # under the same rule as fold; its dims are fold's (one mask for all slices) or the data variable's (one mask per slice, `dim` moved first
+        # like the data)
+        mdims, weights = tuple(cube.dims[mask_var]), np.asarray(cube.data_vars[mask_var])
+        if mdims == tuple(cube.dims['fold']):
+            pass
+        elif mdims == tuple(cube.dims[var]):
+            if mdims[0] != dim:
+                weights = np.moveaxis(weights, mdims.index(dim), 0)
+        else:
+            raise ValueError(f"mask_var {mask_var!r} has dims {mdims}: expected those of 'fold' {tuple(cube.dims['fold'])} or those of "
+                             f"{var!r} {tuple(cube.dims[var])}")
+        mask = np.where(weights <= 1, weights, 1)
     COMPLEX = np.iscomplexobj(data)
 
     with open(os.path.join(out_path, f'parameter_{prefix}.yml'), mode='w', newline='\n') as f:
@@ -168,6 +182,8 @@ def main(argv=sys.argv, return_dataset=False):
             'history': cube.attrs.get('history', '') + f'{SCRIPT}:{metadata["transform_kind"]} {attrs_domain};',
             'text': cube.attrs.get('text', '') + f'\n{TODAY}: {metadata["transform_kind"]} {attrs_domain.upper()}',
         })
+        if mask_var is not None:
+            ds.attrs['mask_var'] = mask_var
         return ds
 
     merged = np.empty_like(data)
@@ -198,7 +214,7 @@ def main(argv=sys.argv, return_dataset=False):
         aux = Psi if TRANSFORM == 'SHEARLET' else None      # :307
         # (straight into the merged cube: no second group-sized result array.  `runtime` of a slice's record is its GROUP's wall time divided by
         # the group's slices -- the reference records a batch's time / its slices; INTEGRATION.md says so)
-        pocs_cube(data[span], mask, results=results, auxiliary_data=aux, out=merged[span], **kwargs)
+        pocs_cube(data[span], mask if mask.ndim == 2 else mask[span], results=results, auxiliary_data=aux, out=merged[span], **kwargs)
         for sl in group:
             block = merged[sl]
             save_cube(wrap(block, sl), create_file_path(coord[sl], prefix=prefix, root_path=out_path, suffix=suffix))

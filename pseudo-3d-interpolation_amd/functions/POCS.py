@@ -421,6 +421,12 @@ def _batch_buffers(device, cube_bytes, mask_bytes):
     return have
 
 
+def _mask_bytes(mask, cap):
+    """Bytes of the device buffer that holds the mask of a batch of up to ``cap`` slices: one slice for a shared ``(nil, nxl)`` mask, ``cap`` slices
+    for a per-slice ``(nslices, nil, nxl)`` one (every batch then uploads its own ``mask[lo:lo + n]``)."""
+    return mask.nbytes if mask.ndim == 2 else mask[:1].nbytes * cap
+
+
 def _active_slices(chunk):
     """``np.count_nonzero(x) != 0`` per slice (POCS.py:515-521), the slices spread over a few threads (NumPy's reductions release the GIL; one thread
     takes ~25 ms per 256 MiB)."""
@@ -543,7 +549,11 @@ class _FFTWorker:
             if w is not None:
                 w.close()
             w = _workers[key] = cls(nil, nxl, step, device, slot)
-        w.m.upload(maskf)
+        if maskf.ndim == 2:
+            w.m.upload(maskf)
+        elif w.m.nbytes < _mask_bytes(maskf, w.capacity):   # a per-slice mask: every chunk brings its own part (run), the buffer grows once
+            w.m.free()
+            w.m = w.plan.alloc(_mask_bytes(maskf, w.capacity))
         return w
 
     def close(self):
@@ -553,7 +563,9 @@ class _FFTWorker:
             if b is not None:
                 b.free()
 
-    def run(self, chunk, dst, sched, niter, thresh_op, version, eps, alpha, before_upload=None, before_download=None):
+    def run(self, chunk, dst, sched, niter, thresh_op, version, eps, alpha, before_upload=None, before_download=None, mask_chunk=None):
+        """``mask_chunk``: the ``(n, nil, nxl)`` float32 masks of the chunk's slices where the job has one mask per slice (None: the shared mask
+        that ``get`` uploaded)."""
         n = chunk.shape[0]
         t0 = time.perf_counter()
         marks = [('start', t0)] if _timeline is not None else None   # tools/e2e_timeline.py: where a chunk's wall time goes
@@ -578,15 +590,21 @@ class _FFTWorker:
             xin = self.hx.view(chunk.shape, dtype)
             _slab_copy(xin, chunk)
             self.x.upload(xin)                         # one upload serves the statistics and the loop
+        per_slice = mask_chunk is not None
+        if per_slice:
+            self.m.upload(mask_chunk)
         mark('h2d')
-        stats = self.plan.prime_dev(self.x.ptr, dt, self.m.ptr, n)   # the statistics pass doubles as the first pass of the job
+        if per_slice:   # (the primed first pass packs ONE mask: plain statistics, and the loop makes its own first pass)
+            stats = self.plan.stats_dev(self.x.ptr, dt, n)
+        else:
+            stats = self.plan.prime_dev(self.x.ptr, dt, self.m.ptr, n)   # the statistics pass doubles as the first pass of the job
         mark('prime')
         active = ~(stats[:, 2] == 0)                   # max|fft2(x)| == 0 <=> np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
         stats[~active] = 1.0                           # keep NaNs of empty slices out of the (unused) schedule rows
         tau = sched(stats)
         mark('schedule')
         done, sums, _ = self.plan.run_dev(self.x.ptr, dt, self.m.ptr, tau, niter, self.o.ptr, n, thresh_op=thresh_op,
-                                          version=version, eps=eps, alpha=alpha, active=active, primed=True)
+                                          version=version, eps=eps, alpha=alpha, active=active, primed=not per_slice, mask_per_slice=per_slice)
         mark('loop')
         if before_download is not None:
             before_download()                          # (the result array's pages are there and page-locked)
@@ -644,16 +662,20 @@ def _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alph
     # wrapper's own and copied once more on the host -- more wall time than its loop
     cap = min(step, nslices)
     itemsize = cube.dtype.itemsize if cube.dtype in _ffi.Plan64._DT else (16 if np.iscomplexobj(cube) else 8)
-    xd, od, md = _batch_buffers(device, nil * nxl * itemsize * cap, mask64.nbytes)
+    xd, od, md = _batch_buffers(device, nil * nxl * itemsize * cap, _mask_bytes(mask64, cap))
+    per_slice = mask64.ndim == 3
     touching = [] if (np.may_share_memory(cube, out) or not out.flags.c_contiguous) else _touch_pages(out)
     try:
-        md.upload(mask64)
+        if not per_slice:
+            md.upload(mask64)
         for lo in range(0, nslices, step):
             chunk = cube[lo:lo + step]
             n = chunk.shape[0]
             t0 = time.perf_counter()
             xc, dt = plan._cube(chunk)
             xd.upload(xc)
+            if per_slice:
+                md.upload(mask64[lo:lo + n])
             active = _active_slices(chunk)   # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
             if thresh_model == 'data-driven':
                 narrow = chunk.astype(np.complex64 if np.iscomplexobj(chunk) else np.float32)
@@ -664,7 +686,8 @@ def _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alph
                 tau = _schedule_from_stats(stats, nil * nxl, thresh_model, niter, p_max, p_min, decay_kind)
             if sqrt_decay:
                 tau = np.sqrt(tau)
-            done, sums, _ = plan.run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active)
+            done, sums, _ = plan.run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active,
+                                         mask_per_slice=per_slice)
             for f in touching:
                 f.result()
             touching = []
@@ -709,8 +732,9 @@ def _pocs_cube_wavelet_double(cube, mask, out, wavelet, niter, thresh_op, thresh
         dst = out[lo:lo + n]
         direct = dst.dtype == xc.dtype and dst.flags.c_contiguous
         res = dst if direct else np.empty_like(xc)
-        done, sums, _ = plan.run_dev(xc.ctypes.data, dt, mask64.ctypes.data, tau, niter, res.ctypes.data, n, thresh_op=thresh_op, version=version, eps=eps,
-                                     alpha=alpha, active=active)
+        mptr = mask64[lo:lo + n].ctypes.data if mask64.ndim == 3 else mask64.ctypes.data   # (a per-slice mask: the batch's own part)
+        done, sums, _ = plan.run_dev(xc.ctypes.data, dt, mptr, tau, niter, res.ctypes.data, n, thresh_op=thresh_op, version=version, eps=eps,
+                                     alpha=alpha, active=active, mask_per_slice=mask64.ndim == 3)
         if not direct:
             dst[...] = res
         runtime = time.perf_counter() - t0
@@ -746,8 +770,9 @@ def _pocs_cube_shearlet_double(cube, mask, out, psi, niter, thresh_op, thresh_mo
         dst = out[lo:lo + n]
         direct = dst.dtype == xc.dtype and dst.flags.c_contiguous
         res = dst if direct else np.empty_like(xc)
-        done, sums, _ = plan.run_dev(xc.ctypes.data, dt, mask64.ctypes.data, tau, niter, res.ctypes.data, n, thresh_op=thresh_op, version=version, eps=eps,
-                                     alpha=alpha, active=active)
+        mptr = mask64[lo:lo + n].ctypes.data if mask64.ndim == 3 else mask64.ctypes.data   # (a per-slice mask: the batch's own part)
+        done, sums, _ = plan.run_dev(xc.ctypes.data, dt, mptr, tau, niter, res.ctypes.data, n, thresh_op=thresh_op, version=version, eps=eps,
+                                     alpha=alpha, active=active, mask_per_slice=mask64.ndim == 3)
         if not direct:
             dst[...] = res
         runtime = time.perf_counter() - t0
@@ -758,13 +783,13 @@ def _pocs_cube_shearlet_double(cube, mask, out, psi, niter, thresh_op, thresh_mo
 
 def _check_cube_args(cube, mask, transform_kind, thresh_op, version, niter, eps, p_max, alpha, p_min):
     """Argument checks of the batched entry points (``pocs_cube``, ``sharding.pocs_block_on_device``), made BEFORE anything is
-    uploaded: the kernels read ``nil * nxl`` mask entries whatever the caller handed over.  Returns the normalised
+    uploaded: the kernels read ``nil * nxl`` mask entries (per slice, for a ``(nslices, nil, nxl)`` mask) whatever the caller handed over.  Returns the normalised
     ``(cube, mask, kind, niter, eps, p_max, alpha, p_min)`` (POCS.py:488-508 for the scalar conversions)."""
     cube = np.asarray(cube)
     if cube.ndim != 3:
         raise ValueError(f'cube must be (nslices, iline, xline), got shape {cube.shape}')
     mask = np.asarray(mask)
-    if mask.shape != cube.shape[1:]:
+    if mask.shape != cube.shape[1:] and mask.shape != cube.shape:   # one mask for all slices, or one per slice
         raise ValueError(f'mask shape {mask.shape} does not match slice shape {cube.shape[1:]}')
     kind = _check_common(mask, transform_kind, thresh_op)
     if version not in _ffi.P3D_VER:
@@ -806,8 +831,11 @@ def pocs_cube(
     like the netCDF cubes of the workflow) with the POCS iteration of ``POCS_algorithm`` -- all slices
     of a batch advance together on the GPU.
 
-    Parameters are those of :func:`POCS_algorithm`; ``mask`` (``(nil, nxl)``) is shared by all slices
-    (cube_POCS_interpolation_3D.py:242-244).  ``results`` (list, optional) receives one dict per
+    Parameters are those of :func:`POCS_algorithm`; ``mask`` is either ``(nil, nxl)``, shared by all slices
+    (cube_POCS_interpolation_3D.py:242-244), or ``(nslices, nil, nxl)``, one mask per slice: slice ``s`` is then interpolated
+    with ``mask[s]`` and its result, ``niterations``, ``cost`` and ``costs`` are those of ``POCS_algorithm(cube[s], mask[s], ...)``
+    (what a mask that carries the slice dimension gives under ``xr.apply_ufunc``).  Every batch uploads its own part of such a
+    mask; the float32 FFT loop runs its unfused passes for it ("Per-slice masks").  ``results`` (list, optional) receives one dict per
     slice with ``niterations``, ``runtime``, ``cost`` and ``costs``.  ``transform`` / ``itransform``
     callables in ``**ignored`` are accepted for signature compatibility and not called: the transform
     is selected by ``transform_kind``.
@@ -886,6 +914,7 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
     nslices, nil, nxl = cube.shape
     step = int(batch_slices) if batch_slices else nslices
     maskf = np.ascontiguousarray(mask, dtype=np.float32)
+    per_slice = maskf.ndim == 3   # one mask per slice: every batch below uploads its own maskf[lo:lo + n]
     precision, want_double = _double_loop_wanted(cube.dtype, nil, nxl, kind, thresh_op, precision, wavelet, ignored.get('transform'), auxiliary_data)
     if want_double and kind == 'WAVELET' and thresh_op in _WAVELET_OPS:
         if decay_kind == 'factors' and not all(s in thresh_model for s in ['inverse', 'proportional']):
@@ -962,7 +991,8 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
                 lo = starts[i]
                 rows.append((lo, workers[w].run(cube[lo:lo + step], out[lo:lo + step], sched, niter, thresh_op, version, eps, alpha,
                                                 before_upload=None if pin is None else (lambda i=i: pin.input_ready(i)),
-                                                before_download=None if pin is None else (lambda i=i: pin.result_ready(i)))))
+                                                before_download=None if pin is None else (lambda i=i: pin.result_ready(i)),
+                                                mask_chunk=maskf[lo:lo + step] if per_slice else None)))
             return rows
 
         try:
@@ -990,16 +1020,19 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
         narrow = np.complex64 if np.iscomplexobj(cube) else np.float32
         per = nil * nxl * np.dtype(narrow).itemsize
         cap = min(step, nslices)
-        xd, od, md = _batch_buffers(device, per * cap, maskf.nbytes)
+        xd, od, md = _batch_buffers(device, per * cap, _mask_bytes(maskf, cap))
         touching = [] if (np.may_share_memory(cube, out) or not out.flags.c_contiguous) else _touch_pages(out)
         try:
-            md.upload(maskf)
+            if not per_slice:
+                md.upload(maskf)
             for lo in range(0, nslices, step):
                 chunk = cube[lo:lo + step]
                 n = chunk.shape[0]
                 t0 = time.perf_counter()
                 xc, dt = plan._cube(chunk)
                 xd.upload(xc)
+                if per_slice:
+                    md.upload(maskf[lo:lo + n])
                 active = _active_slices(chunk)  # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
                 stats = plan.stats_dev(xd.ptr, dt, n)
                 stats[~active] = 1.0      # keep NaNs of empty slices out of the (unused) schedule rows ...
@@ -1011,7 +1044,7 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
                 if sqrt_decay:
                     tau = np.sqrt(tau)  # POCS.py:595
                 done, sums, _ = plan.run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha,
-                                             active=active)
+                                             active=active, mask_per_slice=per_slice)
                 for f in touching:
                     f.result()
                 touching = []
@@ -1031,14 +1064,17 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
     # FFT, the schedules that need the sorted spectrum (or a result array that is not contiguous), and DCT: one batch at a time, resident between
     # one upload and one download like the WAVELET / SHEARLET batches above
     narrow = np.complex64 if np.iscomplexobj(cube) else np.float32
-    xd, od, md = _batch_buffers(device, nil * nxl * np.dtype(narrow).itemsize * min(step, nslices), maskf.nbytes)
-    md.upload(maskf)
+    xd, od, md = _batch_buffers(device, nil * nxl * np.dtype(narrow).itemsize * min(step, nslices), _mask_bytes(maskf, min(step, nslices)))
+    if not per_slice:
+        md.upload(maskf)
     for lo in range(0, nslices, step):
         chunk = cube[lo:lo + step]
         n = chunk.shape[0]
         t0 = time.perf_counter()
         xc, dt = plan._cube(chunk)
         xd.upload(xc)
+        if per_slice:
+            md.upload(maskf[lo:lo + n])
         active = _active_slices(chunk)  # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
         if thresh_model == 'data-driven':
             tau = _data_driven_batch(plan, chunk, active, niter, p_max, p_min, x_dev=xd.ptr if dt == _ffi.P3D_C64 else None)
@@ -1051,7 +1087,8 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
         if sqrt_decay:
             tau = np.sqrt(tau)  # POCS.py:595
         run_dev = partial(plan.dct_run_dev, norm=dct_norm) if kind == 'DCT' else plan.run_dev
-        done, sums, _ = run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active)
+        done, sums, _ = run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active,
+                                mask_per_slice=per_slice)
         dst = out[lo:lo + n]
         if dst.dtype == xc.dtype and dst.flags.c_contiguous:
             od.download_into(dst)

@@ -136,7 +136,8 @@ def pocs_block_on_device(block, mask, device=0, **params):
     ``run_dev``) and the WAVELET / SHEARLET transforms (``WaveletPlan`` / ``ShearletPlan.stats_dev`` + ``run_dev``; BASELINE
     configs[4] is the 8-GPU SHEARLET configuration).  The arguments are checked exactly as ``pocs_cube`` checks them, before
     anything is uploaded.  ``results`` / ``batch_slices`` (per-slice records, caller-chosen chunks), the data-driven schedule and
-    cubes that are neither complex64 nor float32 go through ``pocs_cube`` itself (host arrays) and are uploaded afterwards."""
+    cubes that are neither complex64 nor float32 go through ``pocs_cube`` itself (host arrays) and are uploaded afterwards.  ``mask``: ``(nil, nxl)``
+    or, one mask per slice of the block, ``(n, nil, nxl)``."""
     import torch
 
     from . import _ffi
@@ -169,19 +170,22 @@ def pocs_block_on_device(block, mask, device=0, **params):
     x = _upload(np.ascontiguousarray(block), dev)
     out = torch.empty_like(x)
     m = torch.from_numpy(np.ascontiguousarray(mask, dtype=np.float32)).to(dev)
+    per_slice = m.dim() == 3   # one mask per slice of the block: the loops take it with its slice stride, batch lo starts at mask[lo]
     dt = _ffi.P3D_C64 if np.iscomplexobj(block) else _ffi.P3D_F32
     esz = 8 if dt == _ffi.P3D_C64 else 4
     torch.cuda.synchronize(dev)      # the plans work on their own streams
     common = dict(thresh_op=thresh_op, version=version, eps=eps, alpha=alpha)
     if kind == "FFT":
         plan = P._get_plan(nil, nxl, n, int(device), slot=14)
-        stats = plan.prime_dev(x.data_ptr(), dt, m.data_ptr(), n)
+        # (the primed first pass packs ONE mask: a per-slice job takes plain statistics and the loop makes its own first pass)
+        stats = plan.stats_dev(x.data_ptr(), dt, n) if per_slice else plan.prime_dev(x.data_ptr(), dt, m.data_ptr(), n)
         active = ~(stats[:, 2] == 0)
         stats[~active] = 1.0
         tau = P._schedule_from_stats(stats, nil * nxl, model, niter, p_max, p_min, decay_kind)
         if params.get("sqrt_decay", False):
             tau = np.sqrt(tau)
-        plan.run_dev(x.data_ptr(), dt, m.data_ptr(), tau, niter, out.data_ptr(), n, active=active, primed=True, want_sums=False, **common)
+        plan.run_dev(x.data_ptr(), dt, m.data_ptr(), tau, niter, out.data_ptr(), n, active=active, primed=not per_slice, want_sums=False, mask_per_slice=per_slice,
+                     **common)
         return out
     # WAVELET / SHEARLET: the same statistics -> schedule -> loop as pocs_cube, batch by batch on device pointers
     if kind == "SHEARLET":
@@ -207,7 +211,7 @@ def pocs_block_on_device(block, mask, device=0, **params):
             tau = P._shearlet_schedule_from_stats(stats, (nil, nxl), model, niter, p_max, p_min, decay_kind)
         if params.get("sqrt_decay", False):
             tau = np.sqrt(tau)
-        plan.run_dev(xp, dt, m.data_ptr(), tau, niter, op, nb, active=active, **common)
+        plan.run_dev(xp, dt, m.data_ptr() + (lo * nil * nxl * 4 if per_slice else 0), tau, niter, op, nb, active=active, mask_per_slice=per_slice, **common)
     return out
 
 
@@ -222,6 +226,8 @@ def pocs_cube_sharded(cube, mask, group=None, compute=None, gather="root", out=N
     ``gather='root'`` / ``'all'``: the gathered cube as a NumPy array on rank 0 only (``None`` elsewhere) / on every rank, through ONE
     collective on device tensors.
 
+    ``mask``: ``(nil, nxl)``, handed to every rank as it is, or ``(nslices, nil, nxl)``, cut along the slice axis like the cube.
+
     ``compute(block, mask, **params)`` defaults to the HIP path on device ``LOCAL_RANK``: with a collective the result is kept on the
     device (:func:`pocs_block_on_device`), so that over RCCL the collective moves device tensors and only the gathered cube is
     downloaded; a ``compute`` that returns NumPy (the gloo tests inject one) is gathered on CPU tensors / written to ``out``.
@@ -233,6 +239,10 @@ def pocs_cube_sharded(cube, mask, group=None, compute=None, gather="root", out=N
         raise ValueError("gather must be 'root', 'all' or 'none'")
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     lo, hi = slice_block(cube.shape[0], world, rank)
+    if np.ndim(mask) == 3:   # one mask per slice: every rank takes the part of its block
+        if tuple(np.shape(mask)) != tuple(cube.shape):
+            raise ValueError(f'mask shape {tuple(np.shape(mask))} does not match slice shape {tuple(cube.shape[1:])}')
+        mask = np.asarray(mask[lo:hi])
     on_gpu = dist.get_backend(group) == "nccl"
     local_dev = int(params.pop("device", os.environ.get("LOCAL_RANK", rank)))   # (a caller's device=... wins over LOCAL_RANK)
     if out is not None and (gather != "none" or tuple(out.shape) != tuple(cube.shape) or out.dtype != cube.dtype):
