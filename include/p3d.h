@@ -198,7 +198,7 @@ int p3d_multi_run(int ndev, const int* devices, int nil, int nxl, const void* x_
 /* ---- transform_kind = 'DCT': the loop with scipy.fft.dctn / idctn (type 2) as the sparsifying transform -------------------------
  * norm: the `norm` keyword of both callables.  The DCT is computed from the plan's own batched 2-D FFT of the even/odd-reordered slice
  * plus one pass over groups of four coefficients (csrc/p3d_dct.hip), float32 arithmetic; every shape of p3d_shape_supported is covered.
- * Real cubes run as complex with zero imaginary part. */
+ * Real cubes run as complex with zero imaginary part.  The same loop in double precision: p3d_pocs64_dct_run on a plan64, below. */
 #define P3D_DCT_BACKWARD 0 /* norm=None / 'backward': unnormalised forward, 1/(2 nil * 2 nxl) inverse */
 #define P3D_DCT_ORTHO 1    /* norm='ortho' */
 /* Batched 2-D DCT-II (inverse = 0) / its inverse (inverse = 1) of complex64 slices; test hook like p3d_fft2_c64.  in == out is allowed. */
@@ -234,6 +234,16 @@ int p3d_pocs64_stats(p3d_plan64* plan, const void* x, int dtype, int nslices, do
 int p3d_fft2_c128(p3d_plan64* plan, const void* in_host, void* out_host, int nslices, int inverse);
 int p3d_pocs64_run(p3d_plan64* plan, const void* x, int dtype, const double* mask, const double* tau, const uint8_t* active,
                    const p3d_pocs_params* params, void* out, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms);
+/* ... and with scipy.fft.dctn / idctn (type 2, norm: P3D_DCT_BACKWARD / P3D_DCT_ORTHO) in place of fft2 / ifft2: the passes of the float32 DCT loop in
+ * double on the same plan64 (csrc/p3d_dct64.hip) -- the plan's line-pass fft2 of the even/odd-reordered iterate, one pass over groups of four coefficients
+ * (combine, threshold, split; the factors are doubles), ifft2, and the re-insertion with the reordering folded into its addresses; cost sums without
+ * atomics, so results are bitwise repeatable.  Arguments, host-or-device pointers, dtypes, P3D_FLAG_MASK_PER_SLICE, versions, early exit and error
+ * behaviour are those of p3d_pocs64_stats / p3d_pocs64_run; real cubes run as complex with zero imaginary part. */
+/* test hook: batched dctn (inverse = 0) / idctn (inverse = 1) of HOST complex128 slices through those passes */
+int p3d_dct2_c128(p3d_plan64* plan, const void* in_host, void* out_host, int nslices, int inverse, int norm);
+int p3d_pocs64_dct_stats(p3d_plan64* plan, const void* x, int dtype, int nslices, double* stats_host, int norm);
+int p3d_pocs64_dct_run(p3d_plan64* plan, const void* x, int dtype, const double* mask, const double* tau, const uint8_t* active,
+                       const p3d_pocs_params* params, void* out, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms, int norm);
 
 /* Steps 12 / 14 of the workflow: transform every trace of a (nt, ntraces) time-domain cube (ntraces = nil*nxl, the
  * slice-major layout: sample index slowest) to the frequency domain and back, with the conventions of

@@ -67,6 +67,10 @@ PROTOTYPES = {
     "p3d_fft2_c128": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "p3d_pocs64_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "p3d_dct2_c128": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "p3d_pocs64_dct_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "p3d_pocs64_dct_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int]),
     "p3d_dev_malloc": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.c_size_t]),
     "p3d_dev_free": (C.c_int, [C.c_void_p]),
     "p3d_dev_memcpy": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
@@ -895,6 +899,51 @@ class Plan64(_PlanBase64):
         st = np.empty((n, 6), np.float64)
         check(lib().p3d_pocs64_stats(self.handle, x_ptr, dtype, n, _ptr(st)))
         return st
+
+    # ---- transform_kind = 'DCT' in double precision (csrc/p3d_dct64.hip): hard / soft / garrote, mirroring Plan.dct_* ------------
+    _dct_norm = staticmethod(Plan._dct_norm)
+
+    @staticmethod
+    def _dct_op(thresh_op):
+        if thresh_op not in ("hard", "soft", "garrote"):
+            raise UnsupportedError(P3D_ERR_UNSUPPORTED, f"thresh_op {thresh_op!r}: the double-precision DCT loop has hard, soft and garrote")
+
+    def dct2(self, x, inverse=False, norm=None):
+        """Test hook: scipy.fft.dctn (``inverse``: idctn) of complex128 slices over the last two axes, type 2, through the loop's own passes."""
+        norm = self._dct_norm(norm)
+        xc = np.ascontiguousarray(np.asarray(x, dtype=np.complex128))
+        squeeze = xc.ndim == 2
+        if squeeze:
+            xc = xc[None]
+        if xc.ndim != 3 or xc.shape[1:] != (self.nil, self.nxl) or xc.shape[0] > self.max_slices:
+            raise ValueError(f"expected (<= {self.max_slices}, {self.nil}, {self.nxl}), got {xc.shape}")
+        out = np.empty_like(xc)
+        check(lib().p3d_dct2_c128(self.handle, _ptr(xc), _ptr(out), xc.shape[0], 1 if inverse else 0, norm))
+        return out[0] if squeeze else out
+
+    def dct_stats_dev(self, x_ptr, dtype, n, norm=None):
+        """`stats_dev` of the double-precision ``dctn(x)``; raw pointer (host or device)."""
+        norm = self._dct_norm(norm)
+        st = np.empty((n, 6), np.float64)
+        check(lib().p3d_pocs64_dct_stats(self.handle, x_ptr, dtype, n, _ptr(st), norm))
+        return st
+
+    def dct_run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None, norm=None):
+        """`run` with the DCT pair as the transform.  Returns (out, niter_done, sums, elapsed_ms)."""
+        self._dct_norm(norm)      # (both refusals come before the cube is converted)
+        self._dct_op(thresh_op)
+        xc, dt, m, out = self._host_job(x, mask)
+        done, sums, ms = self.dct_run_dev(xc.ctypes.data, dt, m.ctypes.data, tau, niter, out.ctypes.data, xc.shape[0], thresh_op=thresh_op, version=version,
+                                          eps=eps, alpha=alpha, active=active, norm=norm, mask_per_slice=m.ndim == 3)
+        return out, done, sums, ms
+
+    def dct_run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None,
+                    norm=None, mask_per_slice=False):
+        """`run_dev` with the DCT pair as the transform (pointers host or device).  Returns (niter_done, sums, device ms of the loop)."""
+        norm = self._dct_norm(norm)
+        self._dct_op(thresh_op)
+        return self._run_entry("p3d_pocs64_dct_run", x_ptr, dtype, mask_ptr, tau, niter, out_ptr, n, thresh_op, version, eps, alpha, active,
+                               extra=(norm,), mask_per_slice=mask_per_slice)
 
 
 # ---- SHEARLET variant ----------------------------------------------------------------------

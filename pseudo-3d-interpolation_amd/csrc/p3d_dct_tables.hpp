@@ -29,14 +29,16 @@ inline double scale(int n, int k, int norm)
     return k == 0 ? std::sqrt(1.0 / (4.0 * n)) : std::sqrt(1.0 / (2.0 * n));
 }
 
-// fwd[n], inv[n]: evaluated in double, rounded once
-inline void build_tables(int n, int norm, c32* fwd, c32* inv)
+// fwd[n], inv[n]: evaluated in double, rounded once to the storage type C (c32 for the float32 kernels; a complex of doubles keeps them as they are)
+template <class C>
+inline void build_tables(int n, int norm, C* fwd, C* inv)
 {
+    using R = decltype(C::x);
     for (int k = 0; k < n; ++k) {
         const double ang = 3.14159265358979323846264338327950288 * double(k) / (2.0 * double(n));
         const double s = scale(n, k, norm), c = std::cos(ang), sn = std::sin(ang);
-        fwd[k] = c32{float(s * c), float(-s * sn)};
-        inv[k] = c32{float(c / (2.0 * s)), float(sn / (2.0 * s))};
+        fwd[k] = C{R(s * c), R(-s * sn)};
+        inv[k] = C{R(c / (2.0 * s)), R(sn / (2.0 * s))};
     }
 }
 

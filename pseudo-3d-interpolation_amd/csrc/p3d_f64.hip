@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "p3d.h"
+#include "p3d_f64.hpp"
 #include "p3d_generic.hpp"
 #include "p3d_host.hpp"
 #include "p3d_internal.hpp"
@@ -39,14 +40,11 @@ using p3d::take_x;
 namespace {
 
 using p3d::GenPlan;
-
-struct __attribute__((aligned(16))) c64 {
-    double x, y;
-};
-__device__ __forceinline__ c64 operator+(c64 a, c64 b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ c64 operator-(c64 a, c64 b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ c64 operator*(c64 a, c64 b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ c64 operator*(c64 a, double s) { return {a.x * s, a.y * s}; }
+using p3d::f64::c64;
+using p3d::f64::shrink64;
+using p3d::f64::Fft64;
+using p3d::f64::F64_MAX_PASSES;
+using p3d::f64::F64_THREADS;
 
 constexpr int F64_MAX_N = 5120;
 
@@ -117,28 +115,6 @@ __global__ void line_fft64(const c64* in, c64* out, const c64* tw, GenPlan pl, i
         ns *= R;
     }
     for (int i = threadIdx.x; i < n; i += blockDim.x) out[base + (size_t)i * es] = A[i] * scale;
-}
-
-// threshold_operator.py:9-112 on one coefficient, NumPy's semantics for a complex tau (lexicographic comparisons)
-__device__ __forceinline__ c64 shrink64(c64 X, c64 tau, int op)
-{
-    const double m = hypot(X.x, X.y);   // np.absolute
-    if (op == 0) {                      // hard: where(|X| < tau, 0, X)
-        const bool below = m < tau.x || (m == tau.x && 0.0 < tau.y);
-        return below ? c64{0.0, 0.0} : X;
-    }
-    if (m == 0.0) return c64{0.0, 0.0};   // 1 - tau / 0 = -inf: clipped to 0
-    double gr, gi;
-    if (op == 1) {          // soft: X * clip(1 - tau / |X|, 0)
-        gr = 1.0 - tau.x / m;
-        gi = -tau.y / m;
-    } else {                // garrote: X * clip(1 - tau^2 / |X|^2, 0)
-        const double m2 = m * m;
-        gr = 1.0 - (tau.x * tau.x - tau.y * tau.y) / m2;
-        gi = -(2.0 * tau.x * tau.y) / m2;
-    }
-    const bool keep = (gr > 0.0) || (gr == 0.0 && gi >= 0.0);   // lexicographic max(g, 0)
-    return keep ? X * c64{gr, gi} : c64{0.0, 0.0};
 }
 
 __global__ void shrink64_kernel(c64* w, const c64* tau, int niter, int iter, int op, size_t per_slice, const int* done)
@@ -272,14 +248,6 @@ __global__ void stats64_kernel(const c64* w, double* partial, size_t per_slice)
 // prime factors as direct sums spread over the threads), the twiddle table exp(-2 pi i k / n) beside them when it fits.  The unfused
 // kernels above remain the path of lines too long for that (two buffers + table > 160 KiB) and of P3D_F64_UNFUSED=1.
 // ==================================================================================================================================
-constexpr int F64_MAX_PASSES = 16;
-struct Fft64 {
-    int n, nf;
-    int f[F64_MAX_PASSES];    // radices; 2, 3, 4, 5, 7, 8, 9: in-register butterflies, anything else: direct sums
-    int ns[F64_MAX_PASSES];   // product of the earlier radices = distance of a butterfly's outputs
-    unsigned mg[F64_MAX_PASSES];   // j / ns = umulhi(j, mg) for j < 2^16 (ns > 1)
-};
-
 Fft64 make_fft64(int n)
 {
     Fft64 p{};
@@ -337,10 +305,6 @@ __device__ __forceinline__ c64 tw_at(const c64* tw, int k, int half)
 }
 // a * w (forward) or a * conj(w) (inverse): the table holds exp(-2 pi i k / n)
 template <int DIR> __device__ __forceinline__ c64 twmul(c64 a, c64 w) { return DIR > 0 ? c64{a.x * w.x + a.y * w.y, a.y * w.x - a.x * w.y} : a * w; }
-// a +- i b
-__device__ __forceinline__ c64 add_i(c64 a, c64 b) { return {a.x - b.y, a.y + b.x}; }
-__device__ __forceinline__ c64 sub_i(c64 a, c64 b) { return {a.x + b.y, a.y - b.x}; }
-
 // X[k] = sum_t x[t] W^(t k), W = exp(DIR 2 pi i / R), natural order in and out
 template <int R, int DIR>
 __device__ __forceinline__ void dft_small64(c64 (&x)[R])
@@ -501,7 +465,6 @@ __device__ __forceinline__ c64* tile_fft64(c64* A, c64* B, const c64* tw, int ha
     return A;
 }
 
-constexpr int F64_THREADS = 512;
 enum { C64_ITER = 0, C64_STATS = 1, C64_FWD = 2 };
 
 // Column pass of one tile of LN adjacent columns of a slice.  C64_ITER: forward transform, threshold (tau of the slice and iteration),
@@ -680,35 +643,7 @@ __global__ __launch_bounds__(F64_THREADS) void row64_kernel(c64* work, const c64
 
 }  // namespace
 
-struct p3d_plan64 {
-    int device = 0, nil = 0, nxl = 0, max_slices = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    GenPlan gcol{}, grow{};
-    c64 *tw_col = nullptr, *tw_row = nullptr, *work = nullptr, *tau = nullptr;
-    void *st_x = nullptr, *st_out = nullptr;
-    double *mask = nullptr, *partial = nullptr, *sums = nullptr, *spart = nullptr;
-    size_t mask_cap = 0, mask_stride = 0;   // elements of `mask` (one slice until the first P3D_FLAG_MASK_PER_SLICE job); the stride of the job in progress
-    int* done = nullptr;
-    size_t tau_cap = 0, sums_cap = 0;
-    static constexpr int BLOCKS = 64;
-    size_t per() const { return (size_t)nil * nxl; }
-    // fused passes (col64_kernel / row64_kernel): tiles of ln_col columns / ln_row rows, the twiddle table in LDS where it fits
-    bool fused = false;
-    Fft64 fcol{}, frow{};
-    int ln_col = 0, ln_row = 0, tw_col_lds = 0, tw_row_lds = 0, thr_col = F64_THREADS, thr_row = F64_THREADS;
-    size_t lds_col = 0, lds_row = 0;
-    // passes on the mixed-radix register engine (p3d_mix64.hip) where the axis' length has a plan: chosen per axis, same work buffer
-    const p3d::mix64::Entry *mcol = nullptr, *mrow = nullptr;
-    c64 *tw_mcol = nullptr, *tw_mrow = nullptr;
-    unsigned char* nzflag = nullptr;   // both passes on the register engine: [max_slices][tiles_col] tile flags of the sparse shortcut
-    bool sparse = false;               // ... in use for the job in progress
-    // the observed cube and the result of the job in progress: the caller's own device buffers where it passed such, else the staging buffers
-    const void* cur_x = nullptr;
-    void* cur_out = nullptr;
-    int tiles_col() const { return (nxl + ln_col - 1) / ln_col; }
-    int tiles_row() const { return (nil + ln_row - 1) / ln_row; }
-};
+// (struct p3d_plan64: p3d_f64.hpp)
 
 namespace {
 
@@ -827,7 +762,7 @@ int p3d_plan64_destroy(p3d_plan64* p)
     if (!p) return P3D_OK;
     hipSetDevice(p->device);
     if (p->stream) hipStreamSynchronize(p->stream);
-    void* bufs[] = {p->nzflag, p->tw_mcol, p->tw_mrow, p->tw_col, p->tw_row, p->work, p->tau, p->st_x, p->st_out, p->mask, p->partial, p->sums, p->spart, p->done};
+    void* bufs[] = {p->dct_tab, p->nzflag, p->tw_mcol, p->tw_mrow, p->tw_col, p->tw_row, p->work, p->tau, p->st_x, p->st_out, p->mask, p->partial, p->sums, p->spart, p->done};
     for (void* b : bufs)
         if (b) hipFree(b);
     if (p->ev0) hipEventDestroy(p->ev0);
@@ -924,6 +859,27 @@ static int create64(p3d_plan64** out, int device, int nil, int nxl, int max_slic
 
 int p3d_plan64_create(p3d_plan64** out, int device, int nil, int nxl, int max_slices) { return create64(out, device, nil, nxl, max_slices, false); }
 
+// the per-block statistics records of p->partial ([nslices][nblocks][8]) folded on the host into stats[nslices][P3D_STATS_PER_SLICE]; waits for the stream
+static int fold_stats(p3d_plan64* p, int nslices, int nblocks, double* stats)
+{
+    std::vector<double> host((size_t)nslices * nblocks * 8);
+    P3D_TRY(hipMemcpyAsync(host.data(), p->partial, sizeof(double) * host.size(), hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    for (int s = 0; s < nslices; ++s) {
+        double lr = -INFINITY, li = -INFINITY, mx = 0.0, mn = INFINITY, sq = 0.0;
+        for (int b = 0; b < nblocks; ++b) {
+            const double* q = &host[((size_t)s * nblocks + b) * 8];
+            if (q[0] > lr || (q[0] == lr && q[1] > li)) { lr = q[0]; li = q[1]; }
+            mx = std::fmax(mx, q[2]);
+            mn = std::fmin(mn, q[3]);
+            sq += q[4];
+        }
+        double* o = stats + (size_t)s * P3D_STATS_PER_SLICE;
+        o[0] = lr; o[1] = li; o[2] = mx; o[3] = mn; o[4] = sq; o[5] = 0.0;
+    }
+    return P3D_OK;
+}
+
 // statistics of fft2(x) for the schedule: stats[nslices][P3D_STATS_PER_SLICE] as p3d_pocs_stats (x: host or device pointer)
 int p3d_pocs64_stats(p3d_plan64* p, const void* x, int dtype, int nslices, double* stats)
 {
@@ -943,22 +899,7 @@ int p3d_pocs64_stats(p3d_plan64* p, const void* x, int dtype, int nslices, doubl
         stats64_kernel<<<dim3(p3d_plan64::BLOCKS, nslices), 256, 0, p->stream>>>(p->work, p->partial, p->per());
         P3D_TRY(hipGetLastError());
     }
-    std::vector<double> host((size_t)nslices * nblocks * 8);
-    P3D_TRY(hipMemcpyAsync(host.data(), p->partial, sizeof(double) * host.size(), hipMemcpyDeviceToHost, p->stream));
-    P3D_TRY(hipStreamSynchronize(p->stream));
-    for (int s = 0; s < nslices; ++s) {
-        double lr = -INFINITY, li = -INFINITY, mx = 0.0, mn = INFINITY, sq = 0.0;
-        for (int b = 0; b < nblocks; ++b) {
-            const double* q = &host[((size_t)s * nblocks + b) * 8];
-            if (q[0] > lr || (q[0] == lr && q[1] > li)) { lr = q[0]; li = q[1]; }
-            mx = std::fmax(mx, q[2]);
-            mn = std::fmin(mn, q[3]);
-            sq += q[4];
-        }
-        double* o = stats + (size_t)s * P3D_STATS_PER_SLICE;
-        o[0] = lr; o[1] = li; o[2] = mx; o[3] = mn; o[4] = sq; o[5] = 0.0;
-    }
-    return P3D_OK;
+    return fold_stats(p, nslices, nblocks, stats);
 }
 
 // the loop of POCS_algorithm (POCS.py:560-632) in double precision.  x, out: host or device, dtype as above (x and out alike); mask: host or
@@ -1149,6 +1090,45 @@ int plan64_fft2(p3d_plan64* p, void* buf, int nslices, bool inverse, const int* 
     }
     if ((rc = fft_pass(p, w, w, nslices, false, +1, 1.0 / p->nil, done, done_group))) return rc;
     return fft_pass(p, w, w, nslices, true, +1, 1.0 / p->nxl, done, done_group);
+}
+
+// ---- what p3d_dct64.hip borrows: the line-pass transforms on the work buffer and the loop's small kernels ---------------------------------------------
+// The rows go through the line passes (every extent).  The columns, whose line pass reads 16 bytes per row stride, take the loop's own column kernels as they
+// are where the plan has them: forward the transform-only column pass of the fused loop (tiles of adjacent columns), inverse the register engine's column
+// pass without its threshold (what plan64_shear_back runs) where both extents have a plan there; the line pass otherwise.
+int plan64_fft2_work(p3d_plan64* p, int nslices, bool inverse, const int* done)
+{
+    int rc;
+    if (!inverse) {
+        if ((rc = fft_pass(p, p->work, p->work, nslices, true, -1, 1.0, done))) return rc;
+        if (p->fused) return col_pass64<C64_FWD>(p, nslices, 0, 0, 0, done);
+        return fft_pass(p, p->work, p->work, nslices, false, -1, 1.0, done);
+    }
+    if (p->fused && p->mcol && p->mrow) rc = plan64_shear_cols(p, nullptr, nullptr, nslices, 1, 0, 0, 0, 0, 1, 1.0 / p->nil, done, nullptr, 0);
+    else rc = fft_pass(p, p->work, p->work, nslices, false, +1, 1.0 / p->nil, done);
+    if (rc) return rc;
+    return fft_pass(p, p->work, p->work, nslices, true, +1, 1.0 / p->nxl, done);
+}
+
+int plan64_fold_sums(p3d_plan64* p, double* sums_row, int nslices, int blocks)
+{
+    fold64_kernel<<<nslices, 64, 0, p->stream>>>(p->spart, sums_row, nslices, blocks);
+    P3D_TRY(hipGetLastError());
+    return P3D_OK;
+}
+
+int plan64_converged(p3d_plan64* p, int nslices, int iter, double eps)
+{
+    conv64_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, iter, eps);
+    P3D_TRY(hipGetLastError());
+    return P3D_OK;
+}
+
+int plan64_work_stats(p3d_plan64* p, int nslices, double* stats_host)
+{
+    stats64_kernel<<<dim3(p3d_plan64::BLOCKS, nslices), 256, 0, p->stream>>>(p->work, p->partial, p->per());
+    P3D_TRY(hipGetLastError());
+    return fold_stats(p, nslices, p3d_plan64::BLOCKS, stats_host);
 }
 
 }  // namespace p3d

@@ -99,4 +99,15 @@ int plan64_shear_row_group(p3d_plan64* plan);
 // work (spectra) -> ifft2, re-insertion (POCS.py:616-619), sums_row[slice] = sum |x_new|, result to `out` if write_out; unless last: work = fft2 of the next input
 int plan64_shear_back(p3d_plan64* plan, int dtype, double* sums_row, bool last, int adaptive, int write_out, double alpha, int nslices, const int* done, int zero_fill);
 
+// ---- ... and what the double-precision DCT loop (p3d_dct64.hip) borrows: it runs on a full plan64's own buffers (p3d_f64.hpp) ------------------------------
+// in-place fft2 / ifft2 (numpy.fft conventions) of the first nslices slices of the plan's work buffer (every extent up to 5120: the line passes, the columns
+// on the loop's own column kernels where the plan has them), enqueued on the plan's stream; slice s is skipped where done[s] != 0 (done: device, may be NULL)
+int plan64_fft2_work(p3d_plan64* plan, int nslices, bool inverse, const int* done);
+// sums_row[s] = the `blocks` partial sums of slice s in the plan's spart buffer, added in a fixed order (fold64_kernel)
+int plan64_fold_sums(p3d_plan64* plan, double* sums_row, int nslices, int blocks);
+// the early exit of iteration `iter` on the plan's cost sums (conv64_kernel, POCS.py:622, 631)
+int plan64_converged(p3d_plan64* plan, int nslices, int iter, double eps);
+// statistics of the work buffer's first nslices slices (stats64_kernel) -> stats_host[nslices][P3D_STATS_PER_SLICE]; waits for the plan's stream
+int plan64_work_stats(p3d_plan64* plan, int nslices, double* stats_host);
+
 }  // namespace p3d

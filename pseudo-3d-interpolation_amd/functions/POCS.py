@@ -648,10 +648,12 @@ def _get_plan64(nil, nxl, nslices, device):
 
 
 def _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, results, device,
-                      batch_slices):
+                      batch_slices, kind='FFT', dct_norm=None):
     """``pocs_cube`` through the double-precision loop (``_ffi.Plan64``): statistics of the double-precision ``fft2`` -> the schedule
     (host, complex128, as always) -> the iterations, batch by batch.  The data-driven schedule takes its picks from the float32
-    plan's device sort (positions in the sorted spectrum; the values differ from a double sort's by float32 rounding)."""
+    plan's device sort (positions in the sorted spectrum; the values differ from a double sort's by float32 rounding).
+    ``kind='DCT'``: the same batches through the plan's DCT entries (``dct_norm``: 'backward' or 'ortho'); ``pocs_cube`` has refused the
+    data-driven schedule for it before."""
     nslices, nil, nxl = cube.shape
     step = int(batch_slices) if batch_slices else max(1, min(nslices, (2 << 30) // (nil * nxl * 16)))   # work + staging: 48 B per point and slice
     step = min(step, 65535)   # (plan64's limit: cubes of tiny slices)
@@ -681,13 +683,16 @@ def _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alph
                 narrow = chunk.astype(np.complex64 if np.iscomplexobj(chunk) else np.float32)
                 tau = _data_driven_batch(_get_plan(nil, nxl, n, device, slot=15), narrow, active, niter, p_max, p_min)
             else:
-                stats = plan.stats_dev(xd.ptr, dt, n)
+                stats = plan.dct_stats_dev(xd.ptr, dt, n, norm=dct_norm) if kind == 'DCT' else plan.stats_dev(xd.ptr, dt, n)
                 stats[~active] = 1.0
+                if kind == 'DCT' and dt in (_ffi.P3D_F64, _ffi.P3D_F32):
+                    stats[:, 1] = 0.0  # the DCT of a real slice is real (the complex kernels leave rounding noise in the imaginary part): a real schedule
                 tau = _schedule_from_stats(stats, nil * nxl, thresh_model, niter, p_max, p_min, decay_kind)
             if sqrt_decay:
                 tau = np.sqrt(tau)
-            done, sums, _ = plan.run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active,
-                                         mask_per_slice=per_slice)
+            run_dev = partial(plan.dct_run_dev, norm=dct_norm) if kind == 'DCT' else plan.run_dev
+            done, sums, _ = run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active,
+                                    mask_per_slice=per_slice)
             for f in touching:
                 f.result()
             touching = []
@@ -850,12 +855,14 @@ def pocs_cube(
     cubes too -- it is the faster loop there (fused passes) as well as the reference's arithmetic.  The double-precision loops are
     precision paths (FFT: about a quarter of the float32 rate; WAVELET: per-axis kernels without LDS tiles; SHEARLET: three fused
     passes per iteration where both extents have a plan on the double-precision register engine, a tenth of the float32 rate), have the hard / soft /
-    garrote operators, the FFT and SHEARLET ones slice extents up to 5120;
+    garrote operators, the FFT, DCT and SHEARLET ones slice extents up to 5120 (DCT: with ``precision='reference'`` only, see ``dct_norm``);
     a call that asks for (or implies) double precision outside that coverage runs the float32 kernels and says so with a ``RuntimeWarning``.
 
     ``dct_norm`` (``transform_kind='DCT'``): the ``norm`` of the ``scipy.fft.dctn`` / ``idctn`` pair (type 2) the loop runs -- ``'backward'`` or
     ``'ortho'``.  ``None``: the ``norm`` keyword of a ``transform`` partial handed over in ``**ignored``, else SciPy's default ``'backward'``.  The
-    float32 kernels only; ``thresh_model='data-driven'`` is not available with it.
+    float32 kernels unless ``precision='reference'`` asks for the double-precision DCT loop (hard / soft / garrote, slice extents up to 5120, cubes of all
+    four dtypes, the result in the cube's dtype; the reference's own arithmetic for soft / garrote / FPOCS / APOCS jobs and for double cubes).  complex128 /
+    float64 cubes WITHOUT that argument still run the float32 kernels and say so with the warning.  ``thresh_model='data-driven'`` is not available with it.
 
     ``out`` (optional): an array of the shape and dtype of ``cube`` to write the result into (e.g. a slab of the merged cube of the
     step-13 driver) instead of a new one.
@@ -887,7 +894,9 @@ def _double_loop_wanted(dtype, nil, nxl, kind, thresh_op, precision, wavelet=Non
     the double-precision loops -- explicitly (``'reference'``), by the cube's dtype (complex128 / float64), or because the double-precision loop is the
     only / the faster one for the job: WAVELET banks of more than 64 taps (the float32 tile kernels hold db1 ... db32), SHEARLET on extents that are
     not powers of two but have plans on the double-precision register engine (fused passes there against the float32 loop's unfused ones).  One rule
-    for ``pocs_cube`` and for ``sharding.pocs_block_on_device``."""
+    for ``pocs_cube`` and for ``sharding.pocs_block_on_device``.  Whether a double-precision loop COVERS the job is the caller's business: ``_pocs_cube_locked``
+    sends FFT, WAVELET and SHEARLET jobs there whenever this says so, DCT jobs only for an explicit ``'reference'`` (a complex128 / float64 DCT cube with
+    ``precision=None`` is reported as wanting double precision, warns and runs the float32 kernels)."""
     if precision is None:
         precision = os.environ.get('P3D_PRECISION') or None
     if precision not in (None, 'reference', 'float32'):
@@ -928,14 +937,17 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
             raise ValueError(f'Psi must be ({nil}, {nxl}, nshearlets), got shape {psi.shape}')
         return _pocs_cube_shearlet_double(cube, mask, out, psi, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version,
                                           results, device, batch_slices)
-    if want_double and not (kind == 'FFT' and thresh_op in _WAVELET_OPS and max(nil, nxl) <= 5120):
+    # DCT: the double-precision loop on request only -- complex128 / float64 cubes without precision='reference' keep the float32 kernels (and the warning)
+    asked = kind == 'FFT' or (kind == 'DCT' and precision == 'reference')
+    covered = asked and thresh_op in _WAVELET_OPS and max(nil, nxl) <= 5120
+    if want_double and not covered:
         import warnings
-        why = (f'the {kind} transform' if kind != 'FFT' else f'thresh_op={thresh_op!r}' if thresh_op not in _WAVELET_OPS else f'slice extents above 5120 ({nil} x {nxl})')
+        why = (f'the {kind} transform' if not asked else f'thresh_op={thresh_op!r}' if thresh_op not in _WAVELET_OPS else f'slice extents above 5120 ({nil} x {nxl})')
         warnings.warn(f'double-precision arithmetic was {"requested" if precision == "reference" else "implied by the " + str(cube.dtype) + " cube"}, but the double-precision '
                       f'loop does not cover {why}: this call runs the float32 kernels (pass precision="float32" to say so explicitly)', RuntimeWarning, stacklevel=3)
-    if want_double and kind == 'FFT' and thresh_op in _WAVELET_OPS and max(nil, nxl) <= 5120:
+    if want_double and covered:
         return _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, results,
-                                 device, batch_slices)
+                                 device, batch_slices, kind, dct_norm)
     if kind == 'SHEARLET':
         if auxiliary_data is None:
             raise ValueError(f'{kind} requires pre-computed shearlets in Fourier domain (Psi)')
