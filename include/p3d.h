@@ -225,7 +225,9 @@ int p3d_pocs_dct_run(p3d_plan* plan, const void* x_host, int dtype, const float*
  * of lines in LDS (extents beyond 5088, whose tiles do not fit: six plain passes over the cube).  A precision path, bound by its double-precision
  * butterflies: about a tenth of the float32 rate.  dtype of x and out: P3D_C128, P3D_F64, or P3D_C64 / P3D_F32 (converted on load / store: what the reference's final
  * cast to the input dtype does, cube_POCS_interpolation_3D.py:324); x, out, mask may be host or device pointers; mask is DOUBLE [nil][nxl];
- * tau [nslices][niter][2], stats, sums and the error behaviour as p3d_pocs_stats / p3d_pocs_run; thresh_op: hard, soft, garrote. */
+ * tau [nslices][niter][2], stats, sums and the error behaviour as p3d_pocs_stats / p3d_pocs_run; thresh_op: hard, soft, garrote, each also OR-ed
+ * with P3D_OP_PERCENTILE (p3d_pocs64_run only: tau then holds the percentages, as in p3d_pocs_run; the threshold of a slice and iteration is
+ * np.percentile(|X|, perc) by an exact radix select on the 64-bit moduli with a double interpolation weight, csrc/p3d_select64.hip). */
 typedef struct p3d_plan64 p3d_plan64;
 int p3d_plan64_create(p3d_plan64** out, int device, int nil, int nxl, int max_slices);
 int p3d_plan64_destroy(p3d_plan64* plan);
@@ -234,11 +236,20 @@ int p3d_pocs64_stats(p3d_plan64* plan, const void* x, int dtype, int nslices, do
 int p3d_fft2_c128(p3d_plan64* plan, const void* in_host, void* out_host, int nslices, int inverse);
 int p3d_pocs64_run(p3d_plan64* plan, const void* x, int dtype, const double* mask, const double* tau, const uint8_t* active,
                    const p3d_pocs_params* params, void* out, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms);
+/* test hook: thr_host[s] = np.percentile(|spectrum[s]|, perc_host[s]) of HOST complex128 slices [nslices][nil][nxl] through the loop's own select kernels */
+int p3d_pocs64_percentile(p3d_plan64* plan, const void* spectrum_host_c128, int nslices, const double* perc_host, double* thr_host);
+/* thresh_model = 'data-driven' in double precision: p3d_pocs_sorted_spectrum / p3d_pocs_data_driven_pick above in doubles.  x (host or device, dtype as
+ * p3d_pocs64_run) -> fft2 -> 128-bit lexicographic keys sorted per slice, descending, kept in the plan's work buffer; peaks_host [nslices][2] =
+ * x_fwd.max(); bounds_host [nslices][4] = tau_min (re, im), tau_max (re, im); tau_host [nslices][niter][2] the picks (double pairs), count_host
+ * [nslices] = Nv.  The pick must follow the sort directly (any other call on the plan in between: P3D_ERR_INVALID). */
+int p3d_pocs64_sorted_spectrum(p3d_plan64* plan, const void* x, int dtype, int nslices, double* peaks_host);
+int p3d_pocs64_data_driven_pick(p3d_plan64* plan, int nslices, int niter, const double* bounds_host, double* tau_host, int64_t* count_host);
 /* ... and with scipy.fft.dctn / idctn (type 2, norm: P3D_DCT_BACKWARD / P3D_DCT_ORTHO) in place of fft2 / ifft2: the passes of the float32 DCT loop in
  * double on the same plan64 (csrc/p3d_dct64.hip) -- the plan's line-pass fft2 of the even/odd-reordered iterate, one pass over groups of four coefficients
  * (combine, threshold, split; the factors are doubles), ifft2, and the re-insertion with the reordering folded into its addresses; cost sums without
  * atomics, so results are bitwise repeatable.  Arguments, host-or-device pointers, dtypes, P3D_FLAG_MASK_PER_SLICE, versions, early exit and error
- * behaviour are those of p3d_pocs64_stats / p3d_pocs64_run; real cubes run as complex with zero imaginary part. */
+ * behaviour are those of p3d_pocs64_stats / p3d_pocs64_run (thresh_op: hard, soft, garrote -- no percentile variants); real cubes run as complex with
+ * zero imaginary part. */
 /* test hook: batched dctn (inverse = 0) / idctn (inverse = 1) of HOST complex128 slices through those passes */
 int p3d_dct2_c128(p3d_plan64* plan, const void* in_host, void* out_host, int nslices, int inverse, int norm);
 int p3d_pocs64_dct_stats(p3d_plan64* plan, const void* x, int dtype, int nslices, double* stats_host, int norm);

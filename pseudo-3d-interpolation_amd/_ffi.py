@@ -67,6 +67,9 @@ PROTOTYPES = {
     "p3d_fft2_c128": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "p3d_pocs64_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_int,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "p3d_pocs64_percentile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "p3d_pocs64_sorted_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_pocs64_data_driven_pick": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "p3d_dct2_c128": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "p3d_pocs64_dct_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "p3d_pocs64_dct_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_int,
@@ -899,6 +902,42 @@ class Plan64(_PlanBase64):
         st = np.empty((n, 6), np.float64)
         check(lib().p3d_pocs64_stats(self.handle, x_ptr, dtype, n, _ptr(st)))
         return st
+
+    # ---- order statistics of the double-precision spectrum (csrc/p3d_select64.hip), mirroring Plan's methods ---------------------
+    def percentile(self, spectrum, perc):
+        """Test hook: ``np.percentile(np.abs(spectrum[s]), perc[s])`` per complex128 slice through the loop's own select kernels."""
+        xc = np.ascontiguousarray(np.asarray(spectrum, dtype=np.complex128))
+        if xc.ndim != 3 or xc.shape[1:] != (self.nil, self.nxl) or xc.shape[0] > self.max_slices:
+            raise ValueError(f"expected (<= {self.max_slices}, {self.nil}, {self.nxl}), got {xc.shape}")
+        pc = np.ascontiguousarray(np.broadcast_to(np.asarray(perc, dtype=np.float64), (xc.shape[0],)))
+        thr = np.empty((xc.shape[0],), np.float64)
+        check(lib().p3d_pocs64_percentile(self.handle, _ptr(xc), xc.shape[0], _ptr(pc), _ptr(thr)))
+        return thr
+
+    def sorted_spectrum(self, x):
+        """The double-precision fft2 of every slice, sorted on the device in NumPy's complex order (kept in the plan); returns x_fwd.max() per
+        slice (complex128) -- first half of the 'data-driven' schedule (POCS.py:356-362).  ``x``: a host cube of any of the four dtypes."""
+        xc, dt = self._cube(x)
+        return self.sorted_spectrum_dev(xc.ctypes.data, dt, xc.shape[0])
+
+    def sorted_spectrum_dev(self, x_ptr, dtype, n):
+        """`sorted_spectrum` on a raw pointer (host or device) to ``n`` slices of ``dtype``."""
+        peaks = np.empty((n, 2), np.float64)
+        check(lib().p3d_pocs64_sorted_spectrum(self.handle, C.c_void_p(x_ptr), dtype, n, _ptr(peaks)))
+        return peaks.view(np.complex128)[:, 0]
+
+    def data_driven_pick(self, tau_min, tau_max, niter):
+        """Second half: per slice the number of coefficients strictly between the bounds (complex128, NumPy's order) and the niter
+        thresholds picked from them (POCS.py:359-362); must follow sorted_spectrum directly."""
+        lo = np.ascontiguousarray(tau_min, dtype=np.complex128)
+        hi = np.ascontiguousarray(tau_max, dtype=np.complex128)
+        n = lo.shape[0]
+        bounds = np.empty((n, 4), np.float64)
+        bounds[:, 0], bounds[:, 1], bounds[:, 2], bounds[:, 3] = lo.real, lo.imag, hi.real, hi.imag
+        tau = np.empty((n, int(niter), 2), np.float64)
+        count = np.empty((n,), np.int64)
+        check(lib().p3d_pocs64_data_driven_pick(self.handle, n, int(niter), _ptr(bounds), _ptr(tau), _ptr(count)))
+        return tau.view(np.complex128)[..., 0], count
 
     # ---- transform_kind = 'DCT' in double precision (csrc/p3d_dct64.hip): hard / soft / garrote, mirroring Plan.dct_* ------------
     _dct_norm = staticmethod(Plan._dct_norm)

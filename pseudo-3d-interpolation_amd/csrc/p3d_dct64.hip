@@ -183,6 +183,7 @@ int check(p3d_plan64* p, int nslices, int dtype, int norm)
     if (norm != P3D_DCT_BACKWARD && norm != P3D_DCT_ORTHO) return fail(P3D_ERR_UNSUPPORTED, "DCT norm %d is not implemented (backward, ortho)", norm);
     if (!p->st_x || !p->st_out) return fail(P3D_ERR_INVALID, "the plan has no staging buffers");
     P3D_TRY(hipSetDevice(p->device));
+    p->sorted_slices = 0;   // (every entry overwrites the work buffer: a sorted spectrum kept there is gone)
     if (!p->dct_tab) {   // the factors of both norms, built by the first DCT call on the plan
         const size_t per = 2 * ((size_t)p->nil + p->nxl);
         std::vector<c64> host(2 * per);

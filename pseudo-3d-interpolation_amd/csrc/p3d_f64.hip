@@ -12,7 +12,12 @@
 // lines whose tile does not fit LDS (beyond 5088 points) take the first cut of this file, six plain passes over the cube per iteration built
 // from the pieces of the any-length pipeline (p3d_generic.hip), which P3D_F64_UNFUSED=1 selects for every shape.
 //
-// Entry points (include/p3d.h): p3d_plan64_create / _destroy, p3d_pocs64_stats, p3d_pocs64_run.
+// The percentile operators rank a whole slice between the forward and the inverse column transform: their iteration is the row pass, the
+// forward-only column pass, the select of p3d_select64.hip (its threshold goes to the device-side tau), the threshold pass and the inverse-only
+// column pass.  The 'data-driven' model's sorted spectrum comes from the same unit.
+//
+// Entry points (include/p3d.h): p3d_plan64_create / _destroy, p3d_pocs64_stats, p3d_pocs64_run, p3d_pocs64_sorted_spectrum,
+// p3d_pocs64_data_driven_pick, p3d_pocs64_percentile.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +32,7 @@
 #include "p3d_host.hpp"
 #include "p3d_internal.hpp"
 #include "p3d_mix64.hpp"
+#include "p3d_select64.hpp"
 
 using p3d::fail;
 using p3d::use_device;
@@ -741,8 +747,57 @@ int check64(p3d_plan64* p, int nslices, int dtype)
     if (nslices < 1 || nslices > p->max_slices) return fail(P3D_ERR_INVALID, "nslices = %d outside 1..max_slices (%d)", nslices, p->max_slices);
     if (dtype != P3D_C128 && dtype != P3D_F64 && dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
     P3D_TRY(hipSetDevice(p->device));
+    p->sorted_slices = 0;   // (every entry overwrites the work buffer: a sorted spectrum kept there is gone)
     return P3D_OK;
 }
+
+// inverse transform of the work buffer's columns with 1 / nil, nothing else: the register engine's column pass without its threshold where both extents
+// have a plan there (what plan64_shear_back runs), the line pass otherwise
+int cols_inverse64(p3d_plan64* p, int nslices, const int* done)
+{
+    if (p->fused && p->mcol && p->mrow) return p3d::plan64_shear_cols(p, nullptr, nullptr, nslices, 1, 0, 0, 0, 0, 1, 1.0 / p->nil, done, nullptr, 0);
+    return fft_pass(p, p->work, p->work, nslices, false, +1, 1.0 / p->nil, done);
+}
+
+// The select state of a job with a percentile operator: perc [nslices][niter][2] holds the percentages in its real parts (the layout of tau).
+// Every iteration has its own records [k][s] (p3d_select64.hpp) and weights, written here and uploaded once: no host work inside the loop.
+struct Pct64Job {
+    std::vector<uint64_t> sel;
+    std::vector<double> frac;
+    int nslices = 0;
+    int stage(p3d_plan64* p, const double* perc, int nslices_, int niter)
+    {
+        using namespace p3d::sel64;
+        nslices = nslices_;
+        const size_t per = p->per(), n = (size_t)niter * nslices;
+        sel.assign(n * PCT_WORDS, 0ull);
+        frac.assign(n, 0.0);
+        for (int k = 0; k < niter; ++k)
+            for (int s = 0; s < nslices; ++s) {
+                unsigned lo, hi;
+                p3d::percentile_rank64(perc[2 * ((size_t)s * niter + k)], per, &lo, &hi, &frac[(size_t)k * nslices + s]);
+                uint64_t* me = &sel[((size_t)k * nslices + s) * PCT_WORDS];
+                me[0] = lo;
+                me[2] = hi != lo ? 1ull : 0ull;
+            }
+        int rc;
+        const bool fresh = p->pct_hist_cap < (size_t)p->max_slices * PCT_BINS;
+        if ((rc = grow(p->pct_sel, p->pct_sel_cap, sel.size())) || (rc = grow(p->pct_frac, p->pct_frac_cap, n)) ||
+            (rc = grow(p->pct_mod, p->pct_mod_cap, per * p->max_slices)) || (rc = grow(p->pct_hist, p->pct_hist_cap, (size_t)p->max_slices * PCT_BINS)))
+            return rc;
+        if (fresh) P3D_TRY(hipMemsetAsync(p->pct_hist, 0, sizeof(unsigned) * p->pct_hist_cap, p->stream));   // (every select leaves it all zero)
+        P3D_TRY(hipMemcpyAsync(p->pct_sel, sel.data(), sizeof(uint64_t) * sel.size(), hipMemcpyHostToDevice, p->stream));
+        P3D_TRY(hipMemcpyAsync(p->pct_frac, frac.data(), sizeof(double) * n, hipMemcpyHostToDevice, p->stream));
+        return P3D_OK;
+    }
+    // tau[s][k] <- np.percentile(|work[s]|, perc[s][k]) on the device
+    int select(p3d_plan64* p, int niter, int k, const int* done) const
+    {
+        P3D_TRY(p3d::sel64::percentile64(p->work, p->per(), nslices, p->pct_sel + (size_t)k * nslices * p3d::sel64::PCT_WORDS, p->pct_frac + (size_t)k * nslices,
+                                         p->pct_hist, p->pct_mod, p->tau, niter, k, done, p->stream));
+        return P3D_OK;
+    }
+};
 
 int update(p3d_plan64* p, int dtype, double* sums_row, int mode, int adaptive, int write_out, double alpha, int nslices, const int* done, int zero_fill)
 {
@@ -762,7 +817,7 @@ int p3d_plan64_destroy(p3d_plan64* p)
     if (!p) return P3D_OK;
     hipSetDevice(p->device);
     if (p->stream) hipStreamSynchronize(p->stream);
-    void* bufs[] = {p->dct_tab, p->nzflag, p->tw_mcol, p->tw_mrow, p->tw_col, p->tw_row, p->work, p->tau, p->st_x, p->st_out, p->mask, p->partial, p->sums, p->spart, p->done};
+    void* bufs[] = {p->pct_sel, p->pct_mod, p->pct_frac, p->pct_hist, p->sort_hist, p->dct_tab, p->nzflag, p->tw_mcol, p->tw_mrow, p->tw_col, p->tw_row, p->work, p->tau, p->st_x, p->st_out, p->mask, p->partial, p->sums, p->spart, p->done};
     for (void* b : bufs)
         if (b) hipFree(b);
     if (p->ev0) hipEventDestroy(p->ev0);
@@ -911,7 +966,10 @@ int p3d_pocs64_run(p3d_plan64* p, const void* x, int dtype, const double* mask, 
     if (rc) return rc;
     if (!x || !mask || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
     if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
-    if (prm->thresh_op < P3D_OP_HARD || prm->thresh_op > P3D_OP_GARROTE) return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d: the double-precision path has hard, soft and garrote", prm->thresh_op);
+    const bool percentile = (prm->thresh_op & P3D_OP_PERCENTILE) != 0;
+    const int base_op = prm->thresh_op & ~P3D_OP_PERCENTILE;
+    if (prm->thresh_op < 0 || base_op < P3D_OP_HARD || base_op > P3D_OP_GARROTE)
+        return fail(P3D_ERR_UNSUPPORTED, "thresh_op %d: the double-precision path has hard, soft and garrote and their percentile variants", prm->thresh_op);
     if (prm->version < P3D_VER_REGULAR || prm->version > P3D_VER_ADAPTIVE) return fail(P3D_ERR_INVALID, "unknown version %d", prm->version);
     const int niter = prm->niter;
     const bool early = prm->eps > 0.0, adaptive = prm->version == P3D_VER_ADAPTIVE;
@@ -926,14 +984,30 @@ int p3d_pocs64_run(p3d_plan64* p, const void* x, int dtype, const double* mask, 
     const bool direct_out = choose_out(p, x, out, cube_bytes);
     if ((rc = stage_mask(p->mask, p->mask_cap, mask, per, prm, nslices, p->max_slices, p->stream, &p->mask_stride))) return rc;
     P3D_TRY(hipMemcpyAsync(p->tau, tau, sizeof(c64) * ntau, hipMemcpyHostToDevice, p->stream));   // (Re, Im) pairs of doubles: c64's layout
+    Pct64Job pct;   // (a percentile operator: `tau` holds percentages, the select writes the thresholds over the device copy; lives until collect())
+    if (percentile && (rc = pct.stage(p, tau, nslices, niter))) return rc;
     if ((rc = frame.begin())) return rc;
-    p->sparse = p->nzflag != nullptr;   // (tiles of the spectrum that the threshold empties are neither transformed back, stored nor read again: exact)
-    if (p->fused) {
+    p->sparse = p->nzflag != nullptr && !percentile;   // (tiles of the spectrum that the threshold empties are neither transformed back, stored nor read again: exact)
+    if (p->fused && percentile) {
+        // the select ranks a whole slice: the column pass is split around it -- rows | columns forward | select | threshold | columns inverse
+        if ((rc = row_pass64<R64_FIRST>(p, dtype, p->sums, adaptive ? 1 : 0, 0, prm->alpha, nslices, done_d, 0))) return rc;
+        for (int k = 0; k < niter; ++k) {
+            const bool last = k + 1 == niter;
+            if ((rc = col_pass64<C64_FWD>(p, nslices, 0, 0, 0, done_d)) || (rc = pct.select(p, niter, k, done_d))) return rc;
+            shrink64_kernel<<<dim3(p3d_plan64::BLOCKS * 4, nslices), 256, 0, p->stream>>>(p->work, p->tau, niter, k, base_op, per, done_d);
+            if ((rc = cols_inverse64(p, nslices, done_d))) return rc;
+            double* srow = p->sums + (size_t)(k + 1) * nslices;
+            if (last) rc = row_pass64<R64_LAST>(p, dtype, srow, 0, 1, prm->alpha, nslices, p->done, 1);
+            else rc = row_pass64<R64_MID>(p, dtype, srow, adaptive ? 1 : 0, early ? 1 : 0, prm->alpha, nslices, p->done, 0);
+            if (rc) return rc;
+            if (early) conv64_kernel<<<(nslices + 255) / 256, 256, 0, p->stream>>>(p->sums, p->done, nslices, k, prm->eps);
+        }
+    } else if (p->fused) {
         // two kernels per iteration: rows (inverse transform, re-insertion, forward transform), columns (forward, threshold, inverse)
         if ((rc = row_pass64<R64_FIRST>(p, dtype, p->sums, adaptive ? 1 : 0, 0, prm->alpha, nslices, done_d, 0))) return rc;
         for (int k = 0; k < niter; ++k) {
             const bool last = k + 1 == niter;
-            if ((rc = col_pass64<C64_ITER>(p, nslices, niter, k, prm->thresh_op, done_d))) return rc;
+            if ((rc = col_pass64<C64_ITER>(p, nslices, niter, k, base_op, done_d))) return rc;
             double* srow = p->sums + (size_t)(k + 1) * nslices;
             if (last) rc = row_pass64<R64_LAST>(p, dtype, srow, 0, 1, prm->alpha, nslices, p->done, 1);
             else rc = row_pass64<R64_MID>(p, dtype, srow, adaptive ? 1 : 0, early ? 1 : 0, prm->alpha, nslices, p->done, 0);
@@ -945,7 +1019,8 @@ int p3d_pocs64_run(p3d_plan64* p, const void* x, int dtype, const double* mask, 
     for (int k = 0; k < niter; ++k) {
         const bool last = k + 1 == niter;
         if ((rc = fft2_64(p, nslices, false, done_d))) return rc;
-        shrink64_kernel<<<dim3(p3d_plan64::BLOCKS * 4, nslices), 256, 0, p->stream>>>(p->work, p->tau, niter, k, prm->thresh_op, per, done_d);
+        if (percentile && (rc = pct.select(p, niter, k, done_d))) return rc;
+        shrink64_kernel<<<dim3(p3d_plan64::BLOCKS * 4, nslices), 256, 0, p->stream>>>(p->work, p->tau, niter, k, base_op, per, done_d);
         if ((rc = fft2_64(p, nslices, true, done_d))) return rc;
         if ((rc = update(p, dtype, p->sums + (size_t)(k + 1) * nslices, 1, (adaptive && !last) ? 1 : 0, (early || last) ? 1 : 0, prm->alpha, nslices, p->done,
                          last ? 1 : 0)))
@@ -999,6 +1074,75 @@ int p3d_fft2_c128(p3d_plan64* p, const void* in_host, void* out_host, int nslice
             P3D_TRY(hipMemcpyAsync(out_host, p->work, bytes, hipMemcpyDeviceToHost, p->stream));
         }
     }
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    return P3D_OK;
+}
+
+// test hook: thr[s] = np.percentile(|spectrum[s]|, perc[s]) of HOST complex128 slices through the loop's own select kernels
+int p3d_pocs64_percentile(p3d_plan64* p, const void* spectrum_host, int nslices, const double* perc_host, double* thr_host)
+{
+    int rc = check64(p, nslices, P3D_C128);
+    if (rc) return rc;
+    if (!spectrum_host || !perc_host || !thr_host) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if ((rc = grow(p->tau, p->tau_cap, (size_t)nslices))) return rc;
+    std::vector<double> perc(2 * (size_t)nslices, 0.0);
+    for (int s = 0; s < nslices; ++s) perc[2 * (size_t)s] = perc_host[s];
+    P3D_TRY(hipMemcpyAsync(p->work, spectrum_host, sizeof(c64) * p->per() * nslices, hipMemcpyHostToDevice, p->stream));
+    Pct64Job pct;
+    if ((rc = pct.stage(p, perc.data(), nslices, 1)) || (rc = pct.select(p, 1, 0, nullptr))) return rc;
+    std::vector<c64> thr(nslices);
+    P3D_TRY(hipMemcpyAsync(thr.data(), p->tau, sizeof(c64) * nslices, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    for (int s = 0; s < nslices; ++s) thr_host[s] = thr[s].x;
+    return P3D_OK;
+}
+
+// 'data-driven' schedule (POCS.py:356-362) in double precision without downloading the spectrum: p3d_pocs_sorted_spectrum /
+// p3d_pocs_data_driven_pick in doubles (include/p3d.h, p3d_select64.hip).  The sorted keys stay in the work buffer until the plan's next job.
+int p3d_pocs64_sorted_spectrum(p3d_plan64* p, const void* x, int dtype, int nslices, double* peaks)
+{
+    int rc = check64(p, nslices, dtype);
+    if (rc) return rc;
+    if (!x || !peaks) return fail(P3D_ERR_INVALID, "NULL buffer");
+    if (!p->st_x || !p->st_out) return fail(P3D_ERR_INVALID, "the plan has no staging buffers");
+    const size_t per = p->per();
+    if (per > 0xffffffffull) return fail(P3D_ERR_UNSUPPORTED, "%zu samples per slice: the segmented sort indexes a slice with 32 bits", per);
+    if ((rc = grow(p->sort_hist, p->sort_hist_cap, (size_t)16 * p3d::sel64::sort64_tiles(per) * p->max_slices))) return rc;
+    if ((rc = take_x(p, x, elem_bytes(dtype) * per * nslices))) return rc;
+    p->cur_out = p->st_out;
+    p->sparse = false;
+    if (p->fused) {   // fft2(x) into the work buffer, as p3d_pocs64_stats
+        if ((rc = row_pass64<R64_FIRST>(p, dtype, p->partial, 0, 0, 1.0, nslices, nullptr, 0))) return rc;
+        if ((rc = col_pass64<C64_FWD>(p, nslices, 0, 0, 0, nullptr))) return rc;
+    } else {
+        if ((rc = update(p, dtype, p->partial, 0, 0, 0, 1.0, nslices, nullptr, 0))) return rc;
+        if ((rc = fft2_64(p, nslices, false, nullptr))) return rc;
+    }
+    double* dpeaks = p->partial;   // (free after the transform: 8 doubles per block and slice)
+    P3D_TRY(p3d::sel64::lex_sort_desc64(p->work, p->st_out, per, nslices, p->sort_hist, dpeaks, p->stream));   // keys and sorted keys in work
+    P3D_TRY(hipMemcpyAsync(peaks, dpeaks, sizeof(double) * 2 * nslices, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipStreamSynchronize(p->stream));
+    p->sorted_slices = nslices;
+    return P3D_OK;
+}
+
+int p3d_pocs64_data_driven_pick(p3d_plan64* p, int nslices, int niter, const double* bounds, double* tau, int64_t* count)
+{
+    if (!p) return fail(P3D_ERR_INVALID, "NULL plan");
+    if (!bounds || !tau || !count || niter < 1) return fail(P3D_ERR_INVALID, "NULL buffer or niter < 1");
+    if (p->sorted_slices != nslices || nslices < 1)
+        return fail(P3D_ERR_INVALID, "p3d_pocs64_sorted_spectrum has not just run on %d slices of this plan", nslices);
+    P3D_TRY(hipSetDevice(p->device));
+    // the picks go to the device-side tau, bounds and counts to the (idle) partial sums: [4 nslices doubles | nslices counts]
+    const size_t ntau = (size_t)nslices * niter;
+    if (int rc = grow(p->tau, p->tau_cap, ntau)) return rc;
+    double* dbounds = p->partial;
+    long long* dcount = reinterpret_cast<long long*>(p->partial + 4 * (size_t)nslices);
+    P3D_TRY(hipMemsetAsync(p->tau, 0, sizeof(c64) * ntau, p->stream));
+    P3D_TRY(hipMemcpyAsync(dbounds, bounds, sizeof(double) * 4 * nslices, hipMemcpyHostToDevice, p->stream));
+    P3D_TRY(p3d::sel64::data_driven_pick64(p->work, p->per(), nslices, niter, dbounds, reinterpret_cast<double*>(p->tau), dcount, p->stream));
+    P3D_TRY(hipMemcpyAsync(tau, p->tau, sizeof(c64) * ntau, hipMemcpyDeviceToHost, p->stream));
+    P3D_TRY(hipMemcpyAsync(count, dcount, sizeof(long long) * nslices, hipMemcpyDeviceToHost, p->stream));
     P3D_TRY(hipStreamSynchronize(p->stream));
     return P3D_OK;
 }

@@ -87,6 +87,13 @@ struct p3d_plan64 {
     c64* dct_tab = nullptr;            // transform_kind = 'DCT' (p3d_dct64.hip), built by the first DCT call: [2 norms][fwd nil | inv nil | fwd nxl | inv nxl] in double
     unsigned char* nzflag = nullptr;   // both passes on the register engine: [max_slices][tiles_col] tile flags of the sparse shortcut
     bool sparse = false;               // ... in use for the job in progress
+    // order statistics of the spectrum (p3d_select64.hip), allocated by the first job that needs them: the percentile operators' select state
+    // ([niter][nslices] records and weights), histogram and moduli; the histogram of the 'data-driven' sort
+    uint64_t *pct_sel = nullptr, *pct_mod = nullptr;
+    double* pct_frac = nullptr;
+    unsigned *pct_hist = nullptr, *sort_hist = nullptr;
+    size_t pct_sel_cap = 0, pct_mod_cap = 0, pct_frac_cap = 0, pct_hist_cap = 0, sort_hist_cap = 0;
+    int sorted_slices = 0;             // p3d_pocs64_sorted_spectrum: `work` holds the sorted order keys of that many slices (0: none)
     // the observed cube and the result of the job in progress: the caller's own device buffers where it passed such, else the staging buffers
     const void* cur_x = nullptr;
     void* cur_out = nullptr;

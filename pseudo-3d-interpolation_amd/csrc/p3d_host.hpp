@@ -103,6 +103,18 @@ inline void percentile_rank(double perc, size_t per_slice, unsigned* lo, unsigne
     *frac = (float)(pos - fl);
 }
 
+// ... with the weight in double, for the double-precision loop: NumPy's own (n - 1) q - floor((n - 1) q) (the float above costs about 1e-8)
+inline void percentile_rank64(double perc, size_t per_slice, unsigned* lo, unsigned* hi, double* frac)
+{
+    double pos = (double)(per_slice - 1) * (perc / 100.0);
+    if (!(pos >= 0.0)) pos = 0.0;
+    if (pos > (double)(per_slice - 1)) pos = (double)(per_slice - 1);
+    const double fl = std::floor(pos);
+    *lo = (unsigned)fl;
+    *hi = (unsigned)std::fmin(fl + 1.0, (double)(per_slice - 1));
+    *frac = pos - fl;
+}
+
 // 16 / 8 / 4 bytes per sample of a P3D_C128 / P3D_F64, P3D_C64 / P3D_F32 cube; real cubes
 inline size_t elem_bytes(int dtype) { return dtype == P3D_C128 ? 16 : (dtype == P3D_F64 || dtype == P3D_C64) ? 8 : 4; }
 inline bool real_dtype(int dtype) { return dtype == P3D_F64 || dtype == P3D_F32; }

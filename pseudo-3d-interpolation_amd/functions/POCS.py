@@ -139,6 +139,32 @@ def _data_driven_batch(plan, chunk, active, niter, p_max, p_min, x_dev=None):
     return tau
 
 
+def _data_driven_batch64(plan, chunk, x_ptr, dt, active, niter, p_max, p_min):
+    """`_data_driven_batch` in the cube's own double precision, on a ``_ffi.Plan64`` and the batch that is already resident (``x_ptr``, dtype code
+    ``dt``): the double-precision spectrum is sorted on the device, the bounds are formed here in the reference's arithmetic for the cube's dtype
+    (p * x_fwd.max(): a Python float times a NumPy scalar of the spectrum's dtype -- complex128 from np.fft whatever the cube), the picks are
+    coefficients of the double spectrum, value for value.  p_min='adaptive' takes its bound from np.linalg.norm of the double spectrum
+    (``Plan64.fft2`` of the host batch)."""
+    n = chunk.shape[0]
+    tau = np.zeros((n, niter), np.complex128)
+    live = np.flatnonzero(active)
+    if live.size == 0:
+        return tau
+    if isinstance(p_min, str):
+        X0 = plan.fft2(chunk)
+        for s in live:
+            tau[s] = _data_driven(X0[s], niter, p_max, p_min)
+        return tau
+    peaks = plan.sorted_spectrum_dev(x_ptr, dt, n)           # x_fwd.max() per slice, complex128
+    lo = np.asarray([p_min * pk for pk in peaks])            # POCS.py:293-294
+    hi = np.asarray([p_max * pk for pk in peaks])
+    picks, count = plan.data_driven_pick(lo, hi, niter)
+    if np.any(count[live] == 0):
+        raise IndexError('index 0 is out of bounds for axis 0 with size 0')   # v[0] of an empty selection (POCS.py:360)
+    tau[live] = picks[live]
+    return tau
+
+
 def get_threshold_decay(
     thresh_model,
     niter: int,
@@ -650,8 +676,9 @@ def _get_plan64(nil, nxl, nslices, device):
 def _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, results, device,
                       batch_slices, kind='FFT', dct_norm=None):
     """``pocs_cube`` through the double-precision loop (``_ffi.Plan64``): statistics of the double-precision ``fft2`` -> the schedule
-    (host, complex128, as always) -> the iterations, batch by batch.  The data-driven schedule takes its picks from the float32
-    plan's device sort (positions in the sorted spectrum; the values differ from a double sort's by float32 rounding).
+    (host, complex128, as always) -> the iterations, batch by batch.  The data-driven schedule takes its picks from the plan's own
+    device sort of the double-precision spectrum of the resident batch (``_data_driven_batch64``): coefficients of that spectrum, value for
+    value.  The percentile operators (FFT only) hand their percentages over as the schedule; the loop ranks the moduli itself.
     ``kind='DCT'``: the same batches through the plan's DCT entries (``dct_norm``: 'backward' or 'ortho'); ``pocs_cube`` has refused the
     data-driven schedule for it before."""
     nslices, nil, nxl = cube.shape
@@ -680,8 +707,7 @@ def _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alph
                 md.upload(mask64[lo:lo + n])
             active = _active_slices(chunk)   # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
             if thresh_model == 'data-driven':
-                narrow = chunk.astype(np.complex64 if np.iscomplexobj(chunk) else np.float32)
-                tau = _data_driven_batch(_get_plan(nil, nxl, n, device, slot=15), narrow, active, niter, p_max, p_min)
+                tau = _data_driven_batch64(plan, chunk, xd.ptr, dt, active, niter, p_max, p_min)
             else:
                 stats = plan.dct_stats_dev(xd.ptr, dt, n, norm=dct_norm) if kind == 'DCT' else plan.stats_dev(xd.ptr, dt, n)
                 stats[~active] = 1.0
@@ -855,7 +881,9 @@ def pocs_cube(
     cubes too -- it is the faster loop there (fused passes) as well as the reference's arithmetic.  The double-precision loops are
     precision paths (FFT: about a quarter of the float32 rate; WAVELET: per-axis kernels without LDS tiles; SHEARLET: three fused
     passes per iteration where both extents have a plan on the double-precision register engine, a tenth of the float32 rate), have the hard / soft /
-    garrote operators, the FFT, DCT and SHEARLET ones slice extents up to 5120 (DCT: with ``precision='reference'`` only, see ``dct_norm``);
+    garrote operators -- the FFT one also their percentile variants (an exact select on the double moduli) and every threshold
+    model, ``'data-driven'`` with picks from the double-precision spectrum --, the FFT, DCT and SHEARLET ones slice extents up to 5120 (DCT: with
+    ``precision='reference'`` only, see ``dct_norm``);
     a call that asks for (or implies) double precision outside that coverage runs the float32 kernels and says so with a ``RuntimeWarning``.
 
     ``dct_norm`` (``transform_kind='DCT'``): the ``norm`` of the ``scipy.fft.dctn`` / ``idctn`` pair (type 2) the loop runs -- ``'backward'`` or
@@ -939,10 +967,11 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
                                           results, device, batch_slices)
     # DCT: the double-precision loop on request only -- complex128 / float64 cubes without precision='reference' keep the float32 kernels (and the warning)
     asked = kind == 'FFT' or (kind == 'DCT' and precision == 'reference')
-    covered = asked and thresh_op in _WAVELET_OPS and max(nil, nxl) <= 5120
+    # (FFT: all six operators; DCT: hard / soft / garrote -- the double-precision DCT loop has no percentile select)
+    covered = asked and (kind == 'FFT' or thresh_op in _WAVELET_OPS) and max(nil, nxl) <= 5120
     if want_double and not covered:
         import warnings
-        why = (f'the {kind} transform' if not asked else f'thresh_op={thresh_op!r}' if thresh_op not in _WAVELET_OPS else f'slice extents above 5120 ({nil} x {nxl})')
+        why = (f'the {kind} transform' if not asked else f'thresh_op={thresh_op!r}' if (kind == 'DCT' and thresh_op not in _WAVELET_OPS) else f'slice extents above 5120 ({nil} x {nxl})')
         warnings.warn(f'double-precision arithmetic was {"requested" if precision == "reference" else "implied by the " + str(cube.dtype) + " cube"}, but the double-precision '
                       f'loop does not cover {why}: this call runs the float32 kernels (pass precision="float32" to say so explicitly)', RuntimeWarning, stacklevel=3)
     if want_double and covered:
