@@ -67,10 +67,10 @@ __global__ void gen_line_fft(const c32* in, c32* out, const c32* tw, GenPlan pl,
         const int m = n / R;              // butterflies of this pass
         const int tstep = n / (ns * R);   // tw index of exp(-2*pi*i/(ns*R))
         const int rstep = n / R;          // tw index of exp(-2*pi*i/R)
-        for (int j = threadIdx.x; j < m; j += blockDim.x) {
-            const int jm = j % ns;
-            const int j0 = (j / ns) * ns * R + jm;
-            if (R <= 8) {
+        if (R <= 8) {
+            for (int j = threadIdx.x; j < m; j += blockDim.x) {
+                const int jm = j % ns;
+                const int j0 = (j / ns) * ns * R + jm;
                 switch (R) {
                     case 2: small_butterfly<2>(A, B, tw, j, m, jm, j0, ns, tstep, rstep, dir); break;
                     case 3: small_butterfly<3>(A, B, tw, j, m, jm, j0, ns, tstep, rstep, dir); break;
@@ -79,19 +79,25 @@ __global__ void gen_line_fft(const c32* in, c32* out, const c32* tw, GenPlan pl,
                     case 7: small_butterfly<7>(A, B, tw, j, m, jm, j0, ns, tstep, rstep, dir); break;
                     default: break;  // the factoriser only emits 2, 4 and odd primes
                 }
-            } else {  // large prime factor: direct butterfly, inputs re-read from LDS
-                for (int k = 0; k < R; ++k) {
-                    c32 acc{0.f, 0.f};
-                    for (int t = 0; t < R; ++t) {
-                        // twiddle of the pass and of the butterfly combined: exp(-+2*pi*i*(t*jm*tstep + ((t*k)%R)*rstep)/n)
-                        const long idx = ((long)t * jm * tstep + (long)((long)t * k % R) * rstep) % n;
-                        c32 w = tw[idx];
-                        if (dir > 0) w.y = -w.y;
-                        const c32 pr = A[j + t * m] * w;
-                        acc = acc + pr;
-                    }
-                    B[j0 + k * ns] = acc;
+            }
+        } else {
+            // large prime factor: direct butterfly, inputs re-read from LDS.  The m * R = n outputs of the pass are spread over the threads, not its m
+            // butterflies: a line of prime length has ONE butterfly, whose R^2 terms a single thread used to add (four 821 x 2 slices, 7 iterations: 2.4 s).
+            // Every output is the same sum in the same order whichever thread adds it: the same bits.
+            for (int q = threadIdx.x; q < n; q += blockDim.x) {
+                const int j = q % m, k = q / m;
+                const int jm = j % ns;
+                const int j0 = (j / ns) * ns * R + jm;
+                c32 acc{0.f, 0.f};
+                for (int t = 0; t < R; ++t) {
+                    // twiddle of the pass and of the butterfly combined: exp(-+2*pi*i*(t*jm*tstep + ((t*k)%R)*rstep)/n)
+                    const long idx = ((long)t * jm * tstep + (long)((long)t * k % R) * rstep) % n;
+                    c32 w = tw[idx];
+                    if (dir > 0) w.y = -w.y;
+                    const c32 pr = A[j + t * m] * w;
+                    acc = acc + pr;
                 }
+                B[j0 + k * ns] = acc;
             }
         }
         __syncthreads();
