@@ -23,6 +23,7 @@ There is no CPU fallback for the loop: without the library or without a GPU thes
 import os
 import time
 from functools import partial
+from typing import NamedTuple
 
 import numpy as np
 
@@ -244,40 +245,31 @@ def _schedule_from_stats(stats, size, thresh_model, niter, p_max, p_min, kind):
 #                                      batched GPU entry point
 # =================================================================================================
 _plans = {}
+_shearlet_plans = _plans   # the shearlet plans' former cache of their own, kept as a name for code that resets the caches by name: the one dict
 _workers = {}
 
 
+def _cached_plan(key, nslices, make):
+    """The plan cached under ``key`` if it holds ``nslices`` slices, else a new one, ``make(max(nslices, 1))``, in its place (the old one closed first)."""
+    plan = _plans.get(key)
+    if plan is None or plan.max_slices < nslices:
+        if plan is not None:
+            plan.close()
+        plan = _plans[key] = make(max(nslices, 1))
+    return plan
+
+
 def _get_plan(nil, nxl, nslices, device, slot=0):
-    key = (nil, nxl, device, slot)
-    plan = _plans.get(key)
-    if plan is None or plan.max_slices < nslices:
-        if plan is not None:
-            plan.close()
-        plan = _ffi.Plan(nil, nxl, max(nslices, 1), device)
-        _plans[key] = plan
-    return plan
+    return _cached_plan((nil, nxl, device, slot), nslices, lambda n: _ffi.Plan(nil, nxl, n, device))
 
 
-def _get_wavelet_plan(nil, nxl, nslices, wavelet, device):
-    key = ('wavelet', nil, nxl, str(wavelet), device)
-    plan = _plans.get(key)
-    if plan is None or plan.max_slices < nslices:
-        if plan is not None:
-            plan.close()
-        plan = _ffi.WaveletPlan(nil, nxl, max(nslices, 1), wavelet=wavelet, device=device)
-        _plans[key] = plan
-    return plan
+def _get_plan64(nil, nxl, nslices, device):
+    return _cached_plan(('f64', nil, nxl, device), nslices, lambda n: _ffi.Plan64(nil, nxl, n, device))
 
 
-def _get_wavelet_plan64(nil, nxl, nslices, wavelet, device):
-    key = ('wavelet64', nil, nxl, str(wavelet), device)
-    plan = _plans.get(key)
-    if plan is None or plan.max_slices < nslices:
-        if plan is not None:
-            plan.close()
-        plan = _ffi.WaveletPlan64(nil, nxl, max(nslices, 1), wavelet=wavelet, device=device)
-        _plans[key] = plan
-    return plan
+def _get_wavelet_plan(nil, nxl, nslices, wavelet, device, double=False):
+    tag, cls = ('wavelet64', _ffi.WaveletPlan64) if double else ('wavelet', _ffi.WaveletPlan)
+    return _cached_plan((tag, nil, nxl, str(wavelet), device), nslices, lambda n: cls(nil, nxl, n, wavelet=wavelet, device=device))
 
 
 def _shearlet_adaptive_tau_min(sumsq, shape2d):
@@ -304,34 +296,13 @@ def _shearlet_schedule_from_stats(stats, shape2d, thresh_model, niter, p_max, p_
     return np.reshape(tau, (niter, 1))
 
 
-_shearlet_plans = {}
-
-
-def _get_shearlet_plan(psi, nslices, device):
+def _get_shearlet_plan(psi, nslices, device, double=False):
     """Plans hold the spectra on the device; they are cached per Psi array (identity + shape + a few samples)."""
     psi = np.asarray(psi)
     probe = psi[::max(psi.shape[0] // 7, 1), ::max(psi.shape[1] // 5, 1), ::max(psi.shape[2] // 3, 1)]
     key = (psi.shape, str(psi.dtype), float(np.sum(probe)), float(np.sum(np.abs(probe) ** 2)), device)
-    plan = _shearlet_plans.get(key)
-    if plan is None or plan.max_slices < nslices:
-        if plan is not None:
-            plan.close()
-        plan = _ffi.ShearletPlan(psi, max_slices=max(nslices, 1), device=device)
-        _shearlet_plans[key] = plan
-    return plan
-
-
-def _get_shearlet_plan64(psi, nslices, device):
-    psi = np.asarray(psi)
-    probe = psi[::max(psi.shape[0] // 7, 1), ::max(psi.shape[1] // 5, 1), ::max(psi.shape[2] // 3, 1)]
-    key = ('double', psi.shape, str(psi.dtype), float(np.sum(probe)), float(np.sum(np.abs(probe) ** 2)), device)
-    plan = _shearlet_plans.get(key)
-    if plan is None or plan.max_slices < nslices:
-        if plan is not None:
-            plan.close()
-        plan = _ffi.ShearletPlan64(psi, max_slices=max(nslices, 1), device=device)
-        _shearlet_plans[key] = plan
-    return plan
+    cls = _ffi.ShearletPlan64 if double else _ffi.ShearletPlan
+    return _cached_plan(('double',) + key if double else key, nslices, lambda n: cls(psi, max_slices=n, device=device))
 
 
 def release_plans():
@@ -343,7 +314,7 @@ def release_plans():
         for b in bufs:
             b.free()
     _batch_bufs.clear()
-    for cache in (_plans, _shearlet_plans, _holders):
+    for cache in (_plans, _holders):
         for plan in cache.values():
             plan.close()
         cache.clear()
@@ -662,68 +633,100 @@ def _result_rows(done, sums, runtime):
     return rows
 
 
-def _get_plan64(nil, nxl, nslices, device):
-    key = ('f64', nil, nxl, device)
-    plan = _plans.get(key)
-    if plan is None or plan.max_slices < nslices:
-        if plan is not None:
-            plan.close()
-        plan = _ffi.Plan64(nil, nxl, max(nslices, 1), device)
-        _plans[key] = plan
-    return plan
+class _Job(NamedTuple):
+    """The scalar parameters of one ``pocs_cube`` call as ``_check_cube_args`` normalised them."""
+    niter: int
+    thresh_op: str
+    thresh_model: str
+    eps: float
+    alpha: float
+    p_max: float
+    p_min: object   # a factor, or 'adaptive'
+    sqrt_decay: bool
+    decay_kind: str
+    version: str
 
 
-def _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, results, device,
-                      batch_slices, kind='FFT', dct_norm=None):
-    """``pocs_cube`` through the double-precision loop (``_ffi.Plan64``): statistics of the double-precision ``fft2`` -> the schedule
-    (host, complex128, as always) -> the iterations, batch by batch.  The data-driven schedule takes its picks from the plan's own
-    device sort of the double-precision spectrum of the resident batch (``_data_driven_batch64``): coefficients of that spectrum, value for
-    value.  The percentile operators (FFT only) hand their percentages over as the schedule; the loop ranks the moduli itself.
-    ``kind='DCT'``: the same batches through the plan's DCT entries (``dct_norm``: 'backward' or 'ortho'); ``pocs_cube`` has refused the
-    data-driven schedule for it before."""
-    nslices, nil, nxl = cube.shape
-    step = int(batch_slices) if batch_slices else max(1, min(nslices, (2 << 30) // (nil * nxl * 16)))   # work + staging: 48 B per point and slice
-    step = min(step, 65535)   # (plan64's limit: cubes of tiny slices)
-    plan = _get_plan64(nil, nxl, min(step, nslices), device)
-    mask64 = np.ascontiguousarray(mask, dtype=np.float64)
-    # one upload per batch into device buffers, statistics and loop on the resident copy, the result downloaded straight into `out` (whose fresh
-    # pages a few threads touch meanwhile): a 2-GiB batch of complex128 slices used to be uploaded twice, downloaded into an array of the
-    # wrapper's own and copied once more on the host -- more wall time than its loop
-    cap = min(step, nslices)
-    itemsize = cube.dtype.itemsize if cube.dtype in _ffi.Plan64._DT else (16 if np.iscomplexobj(cube) else 8)
-    xd, od, md = _batch_buffers(device, nil * nxl * itemsize * cap, _mask_bytes(mask64, cap))
-    per_slice = mask64.ndim == 3
-    touching = [] if (np.may_share_memory(cube, out) or not out.flags.c_contiguous) else _touch_pages(out)
+def _tau_of_batch(kind, job, nil, nxl, dct_norm=None):
+    """``tau_of_batch(plan, chunk, x_ptr, dt, n, active)`` of a job: the schedule of one batch -- ``n`` slices of dtype code ``dt`` at ``x_ptr``, where the
+    plan's entries read them (``chunk``: the same slices on the host) -- BEFORE the optional square root.  The statistics entry of the transform, the rows
+    of empty slices kept clean and the schedule function that goes with the transform: one spelling for every batch route of ``pocs_cube`` and for
+    ``sharding.pocs_block_on_device``.  FFT with the data-driven schedule takes its picks from the plan's own device sort of the resident batch's spectrum
+    (a ``_ffi.Plan64``: of the double-precision spectrum, value for value)."""
+    model, niter, p_max, p_min, decay_kind = job.thresh_model, job.niter, job.p_max, job.p_min, job.decay_kind
+
+    def tau_of_batch(plan, chunk, x_ptr, dt, n, active):
+        if kind == 'FFT' and model == 'data-driven':
+            if isinstance(plan, _ffi.Plan64):
+                return _data_driven_batch64(plan, chunk, x_ptr, dt, active, niter, p_max, p_min)
+            return _data_driven_batch(plan, chunk, active, niter, p_max, p_min, x_dev=x_ptr if dt == _ffi.P3D_C64 else None)
+        stats = plan.dct_stats_dev(x_ptr, dt, n, norm=dct_norm) if kind == 'DCT' else plan.stats_dev(x_ptr, dt, n)
+        stats[~active] = 1.0   # keep NaNs of empty slices out of the (unused) schedule rows ...
+        if kind in ('WAVELET', 'SHEARLET'):
+            stats[~active, ..., 1] = 0.0   # ... without making them complex
+            if kind == 'WAVELET':
+                return _wavelet_schedule_from_stats(stats, model, niter, p_max, p_min, decay_kind)
+            return _shearlet_schedule_from_stats(stats, (nil, nxl), model, niter, p_max, p_min, decay_kind)
+        if kind == 'DCT' and dt in (_ffi.P3D_F32, _ffi.P3D_F64):
+            stats[:, 1] = 0.0  # the DCT of a real slice is real (the complex kernels leave rounding noise in the imaginary part): a real schedule
+        return _schedule_from_stats(stats, nil * nxl, model, niter, p_max, p_min, decay_kind)
+    return tau_of_batch
+
+
+def _run_batches(cube, mask, out, plan, step, tau_of_batch, run_dev, job, results, device, resident):
+    """The batch loop of every ``pocs_cube`` route but the chunk pipeline of the statistics-driven float32 FFT jobs: ``step`` slices at a time through
+    ``plan`` -- the batch as the plan takes it (``plan._cube``), its schedule (``tau_of_batch``, see ``_tau_of_batch``; the square root of it with
+    ``sqrt_decay``, POCS.py:595), the iterations (``run_dev``: the plan's run entry), the result into ``out``, one ``_result_rows`` per batch.
+
+    ``resident``: one upload per batch into the device buffers of ``_batch_buffers``, statistics and loop on the resident copy, the result downloaded
+    straight into ``out`` (whose fresh pages a few threads touch while the first batch iterates: a download into untouched pages runs at a third of the
+    link's rate) or, where its dtype or layout differ, through an array of the batch's dtype and an assignment (the reference's final cast,
+    cube_POCS_interpolation_3D.py:324, in either direction).  configs[3]'s cube: 0.10 -> 0.04 s per call (tools/wv_e2e.py) against entry points on host
+    pointers, which upload twice and fill a result array of their own.  Not ``resident`` (the double-precision WAVELET and SHEARLET loops): exactly those
+    entry points, on the caller's own arrays where dtype and layout allow.  A shared mask goes up once, before the first batch; of a mask per slice every
+    batch brings its own part."""
+    nslices = cube.shape[0]
+    mask = np.ascontiguousarray(mask, dtype=plan._MASK_DT)
+    per_slice = mask.ndim == 3
+    touching = []
+    if resident:
+        cap = min(step, nslices)
+        per = plan._cube(cube[:1])[0].nbytes   # a slice as the plan takes it: complex64 / float32 for the float32 plans, all four dtypes for the others
+        xd, od, md = _batch_buffers(device, per * cap, _mask_bytes(mask, cap))
+        # (a caller's `out` that IS the cube -- an in-place call -- holds the input: its pages exist already and must not be written to)
+        touching = [] if (np.may_share_memory(cube, out) or not out.flags.c_contiguous) else _touch_pages(out)
     try:
-        if not per_slice:
-            md.upload(mask64)
+        if resident and not per_slice:
+            md.upload(mask)
         for lo in range(0, nslices, step):
             chunk = cube[lo:lo + step]
             n = chunk.shape[0]
             t0 = time.perf_counter()
             xc, dt = plan._cube(chunk)
-            xd.upload(xc)
-            if per_slice:
-                md.upload(mask64[lo:lo + n])
-            active = _active_slices(chunk)   # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
-            if thresh_model == 'data-driven':
-                tau = _data_driven_batch64(plan, chunk, xd.ptr, dt, active, niter, p_max, p_min)
+            dst = out[lo:lo + n]
+            direct = dst.dtype == xc.dtype and dst.flags.c_contiguous
+            mask_part = mask[lo:lo + n] if per_slice else mask
+            if resident:
+                xd.upload(xc)
+                if per_slice:
+                    md.upload(mask_part)
+                x_ptr, mask_ptr, out_ptr = xd.ptr, md.ptr, od.ptr
             else:
-                stats = plan.dct_stats_dev(xd.ptr, dt, n, norm=dct_norm) if kind == 'DCT' else plan.stats_dev(xd.ptr, dt, n)
-                stats[~active] = 1.0
-                if kind == 'DCT' and dt in (_ffi.P3D_F64, _ffi.P3D_F32):
-                    stats[:, 1] = 0.0  # the DCT of a real slice is real (the complex kernels leave rounding noise in the imaginary part): a real schedule
-                tau = _schedule_from_stats(stats, nil * nxl, thresh_model, niter, p_max, p_min, decay_kind)
-            if sqrt_decay:
-                tau = np.sqrt(tau)
-            run_dev = partial(plan.dct_run_dev, norm=dct_norm) if kind == 'DCT' else plan.run_dev
-            done, sums, _ = run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active,
-                                    mask_per_slice=per_slice)
+                res = dst if direct else np.empty_like(xc)
+                x_ptr, mask_ptr, out_ptr = xc.ctypes.data, mask_part.ctypes.data, res.ctypes.data
+            active = _active_slices(chunk)   # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
+            tau = tau_of_batch(plan, chunk, x_ptr, dt, n, active)
+            if job.sqrt_decay:
+                tau = np.sqrt(tau)  # POCS.py:595
+            done, sums, _ = run_dev(x_ptr, dt, mask_ptr, tau, job.niter, out_ptr, n, thresh_op=job.thresh_op, version=job.version, eps=job.eps,
+                                    alpha=job.alpha, active=active, mask_per_slice=per_slice)
             for f in touching:
                 f.result()
             touching = []
-            dst = out[lo:lo + n]
-            if dst.dtype == xc.dtype and dst.flags.c_contiguous:
+            if not resident:
+                if not direct:
+                    dst[...] = res
+            elif direct:
                 od.download_into(dst)
             else:
                 dst[...] = od.download(xc.shape, xc.dtype)
@@ -733,82 +736,6 @@ def _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alph
     finally:
         for f in touching:
             f.result()
-    return out
-
-
-def _pocs_cube_wavelet_double(cube, mask, out, wavelet, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, results, device,
-                              batch_slices):
-    """``pocs_cube`` for the WAVELET transform through the double-precision loop (``_ffi.WaveletPlan64``): statistics of the double-precision
-    decomposition -> the schedule (host, as always) -> the iterations, batch by batch; complex64 / float32 cubes are widened on load and the
-    result is cast back on store (the reference's final cast, cube_POCS_interpolation_3D.py:324)."""
-    nslices, nil, nxl = cube.shape
-    # coefficient vector, feed, row / column intermediates, approximations and reconstructions of every level, staging: ~7.5 slice-sized arrays of
-    # 16-byte elements
-    step = int(batch_slices) if batch_slices else max(1, min(nslices, (4 << 30) // (nil * nxl * 120)))
-    step = min(step, 65535, nslices)
-    plan = _get_wavelet_plan64(nil, nxl, step, wavelet, device)
-    mask64 = np.ascontiguousarray(mask, dtype=np.float64)
-    for lo in range(0, nslices, step):
-        chunk = cube[lo:lo + step]
-        n = chunk.shape[0]
-        t0 = time.perf_counter()
-        xc, dt = plan._cube(chunk)
-        active = _active_slices(chunk)   # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
-        stats = plan.stats_dev(xc.ctypes.data, dt, n)
-        stats[~active] = 1.0       # keep NaNs of empty slices out of the (unused) schedule rows ...
-        stats[~active, ..., 1] = 0.0   # ... without making them complex
-        tau = _wavelet_schedule_from_stats(stats, thresh_model, niter, p_max, p_min, decay_kind)
-        if sqrt_decay:
-            tau = np.sqrt(tau)  # POCS.py:595
-        dst = out[lo:lo + n]
-        direct = dst.dtype == xc.dtype and dst.flags.c_contiguous
-        res = dst if direct else np.empty_like(xc)
-        mptr = mask64[lo:lo + n].ctypes.data if mask64.ndim == 3 else mask64.ctypes.data   # (a per-slice mask: the batch's own part)
-        done, sums, _ = plan.run_dev(xc.ctypes.data, dt, mptr, tau, niter, res.ctypes.data, n, thresh_op=thresh_op, version=version, eps=eps,
-                                     alpha=alpha, active=active, mask_per_slice=mask64.ndim == 3)
-        if not direct:
-            dst[...] = res
-        runtime = time.perf_counter() - t0
-        if results is not None:
-            results.extend(_result_rows(done, sums, runtime))
-    return out
-
-
-def _pocs_cube_shearlet_double(cube, mask, out, psi, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, results, device,
-                               batch_slices):
-    """``pocs_cube`` for the SHEARLET transform through the double-precision loop (``_ffi.ShearletPlan64``), batch by batch as
-    ``_pocs_cube_wavelet_double``: statistics of the double-precision coefficients -> the schedule (host) -> the iterations; complex64 / float32
-    cubes are widened on load and the result is cast back on store (the reference's final cast, cube_POCS_interpolation_3D.py:324)."""
-    nslices, nil, nxl = cube.shape
-    nsh = psi.shape[2]
-    # coefficients of one slice are nsh full-size complex128 arrays on the device: bound the batch by memory (<= 16 GiB of coefficients)
-    fit = max(1, min(int((16 << 30) // (nsh * nil * nxl * 16)), 65535 // nsh))
-    step = min(int(batch_slices) if batch_slices else nslices, fit, nslices)
-    plan = _get_shearlet_plan64(psi, step, device)
-    mask64 = np.ascontiguousarray(mask, dtype=np.float64)
-    for lo in range(0, nslices, step):
-        chunk = cube[lo:lo + step]
-        n = chunk.shape[0]
-        t0 = time.perf_counter()
-        xc, dt = plan._cube(chunk)
-        active = _active_slices(chunk)   # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
-        stats = plan.stats_dev(xc.ctypes.data, dt, n)
-        stats[~active] = 1.0
-        stats[~active, ..., 1] = 0.0
-        tau = _shearlet_schedule_from_stats(stats, (nil, nxl), thresh_model, niter, p_max, p_min, decay_kind)
-        if sqrt_decay:
-            tau = np.sqrt(tau)  # POCS.py:595
-        dst = out[lo:lo + n]
-        direct = dst.dtype == xc.dtype and dst.flags.c_contiguous
-        res = dst if direct else np.empty_like(xc)
-        mptr = mask64[lo:lo + n].ctypes.data if mask64.ndim == 3 else mask64.ctypes.data   # (a per-slice mask: the batch's own part)
-        done, sums, _ = plan.run_dev(xc.ctypes.data, dt, mptr, tau, niter, res.ctypes.data, n, thresh_op=thresh_op, version=version, eps=eps,
-                                     alpha=alpha, active=active, mask_per_slice=mask64.ndim == 3)
-        if not direct:
-            dst[...] = res
-        runtime = time.perf_counter() - t0
-        if results is not None:
-            results.extend(_result_rows(done, sums, runtime))
     return out
 
 
@@ -899,6 +826,7 @@ def pocs_cube(
     """
     cube, mask, kind, niter, eps, p_max, alpha, p_min = _check_cube_args(cube, mask, transform_kind, thresh_op, version, niter, eps,
                                                                          p_max, alpha, p_min)
+    job = _Job(niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version)
     if out is None:
         out = np.empty_like(cube)
     elif not isinstance(out, np.ndarray) or out.shape != cube.shape or out.dtype != cube.dtype:
@@ -913,8 +841,7 @@ def pocs_cube(
     # device + stream"): calls on ONE device take turns -- a threaded caller (dask's threaded scheduler under xr.apply_ufunc) gets the same
     # results as a serial one; calls on different devices run side by side.
     with _device_lock(device):
-        return _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version,
-                                 results, device, batch_slices, wavelet, auxiliary_data, precision, out, ignored, dct_norm)
+        return _pocs_cube_locked(cube, mask, kind, job, results, device, batch_slices, wavelet, auxiliary_data, precision, out, ignored, dct_norm)
 
 
 def _double_loop_wanted(dtype, nil, nxl, kind, thresh_op, precision, wavelet=None, transform=None, auxiliary_data=None):
@@ -945,61 +872,66 @@ def _double_loop_wanted(dtype, nil, nxl, kind, thresh_op, precision, wavelet=Non
     return precision, want_double
 
 
-def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, results, device,
-                      batch_slices, wavelet, auxiliary_data, precision, out, ignored, dct_norm=None):
-    """``pocs_cube`` behind its argument checks, with the device's lock held."""
+def _pocs_cube_locked(cube, mask, kind, job, results, device, batch_slices, wavelet, auxiliary_data, precision, out, ignored, dct_norm=None):
+    """``pocs_cube`` behind its argument checks, with the device's lock held: decide the route, raise or warn, build the plan and the schedule of a
+    batch, run the batches."""
+    niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version = job
     nslices, nil, nxl = cube.shape
-    step = int(batch_slices) if batch_slices else nslices
-    maskf = np.ascontiguousarray(mask, dtype=np.float32)
-    per_slice = maskf.ndim == 3   # one mask per slice: every batch below uploads its own maskf[lo:lo + n]
     precision, want_double = _double_loop_wanted(cube.dtype, nil, nxl, kind, thresh_op, precision, wavelet, ignored.get('transform'), auxiliary_data)
-    if want_double and kind == 'WAVELET' and thresh_op in _WAVELET_OPS:
-        if decay_kind == 'factors' and not all(s in thresh_model for s in ['inverse', 'proportional']):
-            raise IndexError('list index out of range (decay_kind="factors" yields one tau per iteration, the WAVELET '
-                             'thresholding needs one per level and detail)')   # (as the float32 path below: the reference fails here)
-        return _pocs_cube_wavelet_double(cube, mask, out, _wavelet_name(ignored.get('transform'), wavelet), niter, thresh_op, thresh_model, eps, alpha, p_max,
-                                         p_min, sqrt_decay, decay_kind, version, results, device, batch_slices)
-    if want_double and kind == 'SHEARLET' and thresh_op in _WAVELET_OPS and auxiliary_data is not None and max(nil, nxl) <= 5120:
-        psi = np.asarray(auxiliary_data)
-        if psi.ndim != 3 or psi.shape[:2] != (nil, nxl):
-            raise ValueError(f'Psi must be ({nil}, {nxl}, nshearlets), got shape {psi.shape}')
-        return _pocs_cube_shearlet_double(cube, mask, out, psi, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version,
-                                          results, device, batch_slices)
-    # DCT: the double-precision loop on request only -- complex128 / float64 cubes without precision='reference' keep the float32 kernels (and the warning)
+    # The double-precision loops: WAVELET and SHEARLET have hard / soft / garrote; FFT all six operators; DCT hard / soft / garrote (no percentile select) and
+    # on request only -- complex128 / float64 cubes without precision='reference' keep the float32 kernels (and the warning); slice extents up to 5120
+    plain = thresh_op in _WAVELET_OPS
     asked = kind == 'FFT' or (kind == 'DCT' and precision == 'reference')
-    # (FFT: all six operators; DCT: hard / soft / garrote -- the double-precision DCT loop has no percentile select)
-    covered = asked and (kind == 'FFT' or thresh_op in _WAVELET_OPS) and max(nil, nxl) <= 5120
-    if want_double and not covered:
+    if kind == 'WAVELET':
+        double = want_double and plain
+    elif kind == 'SHEARLET':
+        double = want_double and plain and auxiliary_data is not None and max(nil, nxl) <= 5120
+    else:
+        double = want_double and asked and (kind == 'FFT' or plain) and max(nil, nxl) <= 5120
+    if want_double and not double:
         import warnings
         why = (f'the {kind} transform' if not asked else f'thresh_op={thresh_op!r}' if (kind == 'DCT' and thresh_op not in _WAVELET_OPS) else f'slice extents above 5120 ({nil} x {nxl})')
         warnings.warn(f'double-precision arithmetic was {"requested" if precision == "reference" else "implied by the " + str(cube.dtype) + " cube"}, but the double-precision '
                       f'loop does not cover {why}: this call runs the float32 kernels (pass precision="float32" to say so explicitly)', RuntimeWarning, stacklevel=3)
-    if want_double and covered:
-        return _pocs_cube_double(cube, mask, out, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, results,
-                                 device, batch_slices, kind, dct_norm)
+    step = int(batch_slices) if batch_slices else nslices
+    if not double:
+        maskf = np.ascontiguousarray(mask, dtype=np.float32)
+        per_slice = maskf.ndim == 3   # one mask per slice: every batch below uploads its own maskf[lo:lo + n]
     if kind == 'SHEARLET':
         if auxiliary_data is None:
             raise ValueError(f'{kind} requires pre-computed shearlets in Fourier domain (Psi)')
-        if thresh_op not in _WAVELET_OPS:
+        if not plain:
             raise NotImplementedError(f'thresh_op {thresh_op!r} is not available for the SHEARLET transform')
         psi = np.asarray(auxiliary_data)
         if psi.ndim != 3 or psi.shape[:2] != (nil, nxl):
             raise ValueError(f'Psi must be ({nil}, {nxl}, nshearlets), got shape {psi.shape}')
-        # coefficients of one slice are nsh full-size arrays on the device: bound the batch by memory (<= 8 GiB of coefficients)
+        # coefficients of one slice are nsh full-size arrays on the device: bound the batch by memory (<= 8 GiB of complex64 coefficients, <= 16 GiB of
+        # complex128 ones: the same number of slices)
         fit = max(1, min(int((8 << 30) // (psi.shape[2] * nil * nxl * 8)), 65535 // psi.shape[2]))
         step = min(step, fit)
-        plan = _get_shearlet_plan(psi, min(step, nslices), device)
+        plan = _get_shearlet_plan(psi, min(step, nslices), device, double)
     elif kind == 'WAVELET':
-        if thresh_op not in _WAVELET_OPS:  # threshold_wavelet (POCS.py:105-166) has no percentile variants
+        if not plain:  # threshold_wavelet (POCS.py:105-166) has no percentile variants
             raise NotImplementedError(f'thresh_op {thresh_op!r} is not available for the WAVELET transform')
         if decay_kind == 'factors' and not all(s in thresh_model for s in ['inverse', 'proportional']):
             # the reference builds a (niter, 1, 1) schedule here and threshold_wavelet (POCS.py:135-166) then indexes it per
             # level and detail: it fails for every decomposition; keep the failure instead of inventing a behaviour
             raise IndexError('list index out of range (decay_kind="factors" yields one tau per iteration, the WAVELET '
                              'thresholding needs one per level and detail)')
-        plan = _get_wavelet_plan(nil, nxl, min(step, nslices), _wavelet_name(ignored.get('transform'), wavelet), device)
+        if double:
+            # coefficient vector, feed, row / column intermediates, approximations and reconstructions of every level, staging: ~7.5 slice-sized arrays of
+            # 16-byte elements
+            if not batch_slices:
+                step = max(1, min(nslices, (4 << 30) // (nil * nxl * 120)))
+            step = min(step, 65535)
+        plan = _get_wavelet_plan(nil, nxl, min(step, nslices), _wavelet_name(ignored.get('transform'), wavelet), device, double)
+    elif double:
+        if not batch_slices:
+            step = max(1, min(nslices, (2 << 30) // (nil * nxl * 16)))   # work + staging: 48 B per point and slice
+        step = min(step, 65535)   # (plan64's limit: cubes of tiny slices)
+        plan = _get_plan64(nil, nxl, min(step, nslices), device)
     elif kind == 'DCT':
-        plan = _get_plan(nil, nxl, min(step, nslices), device, slot=15)   # the FFT plan: the DCT runs on its transforms (batch loop at the end)
+        plan = _get_plan(nil, nxl, min(step, nslices), device, slot=15)   # the FFT plan: the DCT runs on its transforms
     elif thresh_model != 'data-driven' and out.flags.c_contiguous:
         # FFT, statistics-driven schedules: chunks go through device buffers, uploaded once each, two chunks in flight
         slice_bytes = nil * nxl * (8 if np.iscomplexobj(cube) else 4)
@@ -1053,92 +985,11 @@ def _pocs_cube_locked(cube, mask, kind, niter, thresh_op, thresh_model, eps, alp
     else:
         plan = _get_plan(nil, nxl, min(step, nslices), device, slot=15)   # the low slots belong to the chunk workers
 
-    if kind in ('WAVELET', 'SHEARLET'):
-        # One upload per batch, statistics and loop on the device-resident copy, the result downloaded straight into `out` (whose fresh
-        # pages a few threads touch while the batch iterates: a download into untouched pages runs at a third of the link's rate).
-        # configs[3]'s cube: 0.10 -> 0.04 s per call (tools/wv_e2e.py); the entry points took host pointers before: two uploads,
-        # a result array of their own and a copy of it.
-        narrow = np.complex64 if np.iscomplexobj(cube) else np.float32
-        per = nil * nxl * np.dtype(narrow).itemsize
-        cap = min(step, nslices)
-        xd, od, md = _batch_buffers(device, per * cap, _mask_bytes(maskf, cap))
-        touching = [] if (np.may_share_memory(cube, out) or not out.flags.c_contiguous) else _touch_pages(out)
-        try:
-            if not per_slice:
-                md.upload(maskf)
-            for lo in range(0, nslices, step):
-                chunk = cube[lo:lo + step]
-                n = chunk.shape[0]
-                t0 = time.perf_counter()
-                xc, dt = plan._cube(chunk)
-                xd.upload(xc)
-                if per_slice:
-                    md.upload(maskf[lo:lo + n])
-                active = _active_slices(chunk)  # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
-                stats = plan.stats_dev(xd.ptr, dt, n)
-                stats[~active] = 1.0      # keep NaNs of empty slices out of the (unused) schedule rows ...
-                stats[~active, ..., 1] = 0.0  # ... without making them complex
-                if kind == 'WAVELET':
-                    tau = _wavelet_schedule_from_stats(stats, thresh_model, niter, p_max, p_min, decay_kind)
-                else:
-                    tau = _shearlet_schedule_from_stats(stats, (nil, nxl), thresh_model, niter, p_max, p_min, decay_kind)
-                if sqrt_decay:
-                    tau = np.sqrt(tau)  # POCS.py:595
-                done, sums, _ = plan.run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha,
-                                             active=active, mask_per_slice=per_slice)
-                for f in touching:
-                    f.result()
-                touching = []
-                dst = out[lo:lo + n]
-                if dst.dtype == xc.dtype and dst.flags.c_contiguous:
-                    od.download_into(dst)
-                else:
-                    dst[...] = od.download(xc.shape, xc.dtype)   # (a double-precision cube: the reference's final cast, the other way round)
-                runtime = time.perf_counter() - t0
-                if results is not None:
-                    results.extend(_result_rows(done, sums, runtime))
-        finally:
-            for f in touching:
-                f.result()
-        return out
-
-    # FFT, the schedules that need the sorted spectrum (or a result array that is not contiguous), and DCT: one batch at a time, resident between
-    # one upload and one download like the WAVELET / SHEARLET batches above
-    narrow = np.complex64 if np.iscomplexobj(cube) else np.float32
-    xd, od, md = _batch_buffers(device, nil * nxl * np.dtype(narrow).itemsize * min(step, nslices), _mask_bytes(maskf, min(step, nslices)))
-    if not per_slice:
-        md.upload(maskf)
-    for lo in range(0, nslices, step):
-        chunk = cube[lo:lo + step]
-        n = chunk.shape[0]
-        t0 = time.perf_counter()
-        xc, dt = plan._cube(chunk)
-        xd.upload(xc)
-        if per_slice:
-            md.upload(maskf[lo:lo + n])
-        active = _active_slices(chunk)  # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
-        if thresh_model == 'data-driven':
-            tau = _data_driven_batch(plan, chunk, active, niter, p_max, p_min, x_dev=xd.ptr if dt == _ffi.P3D_C64 else None)
-        else:
-            stats = plan.dct_stats_dev(xd.ptr, dt, n, norm=dct_norm) if kind == 'DCT' else plan.stats_dev(xd.ptr, dt, n)
-            stats[~active] = 1.0  # keep NaNs of empty slices out of the (unused) schedule rows
-            if kind == 'DCT' and dt == _ffi.P3D_F32:
-                stats[:, 1] = 0.0  # the DCT of a real slice is real (the complex kernels leave rounding noise in the imaginary part): a real schedule
-            tau = _schedule_from_stats(stats, nil * nxl, thresh_model, niter, p_max, p_min, decay_kind)
-        if sqrt_decay:
-            tau = np.sqrt(tau)  # POCS.py:595
-        run_dev = partial(plan.dct_run_dev, norm=dct_norm) if kind == 'DCT' else plan.run_dev
-        done, sums, _ = run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, n, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha, active=active,
-                                mask_per_slice=per_slice)
-        dst = out[lo:lo + n]
-        if dst.dtype == xc.dtype and dst.flags.c_contiguous:
-            od.download_into(dst)
-        else:
-            dst[...] = od.download(xc.shape, xc.dtype)
-        runtime = time.perf_counter() - t0
-        if results is not None:
-            results.extend(_result_rows(done, sums, runtime))
-    return out
+    # Everything but the chunk pipeline above: one batch at a time, resident between one upload and one download (FFT: the schedules that need the
+    # sorted spectrum, or a result array that is not contiguous) -- but for the double-precision WAVELET and SHEARLET loops, which take host pointers
+    run_dev = partial(plan.dct_run_dev, norm=dct_norm) if kind == 'DCT' else plan.run_dev
+    return _run_batches(cube, mask if double else maskf, out, plan, step, _tau_of_batch(kind, job, nil, nxl, dct_norm), run_dev, job, results, device,
+                        resident=not (double and kind in ('WAVELET', 'SHEARLET')))
 
 
 # =================================================================================================

@@ -197,19 +197,15 @@ def pocs_block_on_device(block, mask, device=0, **params):
     else:
         step = n
         plan = P._get_wavelet_plan(nil, nxl, n, P._wavelet_name(params.get("transform"), params.get("wavelet")), int(device))
+    job = P._Job(niter, thresh_op, model, eps, alpha, p_max, p_min, params.get("sqrt_decay", False), decay_kind, version)
+    tau_of_batch = P._tau_of_batch(kind, job, nil, nxl)
     per = nil * nxl * esz
     for lo in range(0, n, step):
         nb = min(step, n - lo)
         xp, op = x.data_ptr() + lo * per, out.data_ptr() + lo * per
-        stats = plan.stats_dev(xp, dt, nb)
         active = (x[lo:lo + nb].reshape(nb, -1) != 0).any(dim=1).cpu().numpy()   # np.count_nonzero(x) == 0 -> untouched (POCS.py:515-521)
-        stats[~active] = 1.0
-        stats[~active, ..., 1] = 0.0
-        if kind == "WAVELET":
-            tau = P._wavelet_schedule_from_stats(stats, model, niter, p_max, p_min, decay_kind)
-        else:
-            tau = P._shearlet_schedule_from_stats(stats, (nil, nxl), model, niter, p_max, p_min, decay_kind)
-        if params.get("sqrt_decay", False):
+        tau = tau_of_batch(plan, None, xp, dt, nb, active)   # (the statistics-driven schedules read the device copy only)
+        if job.sqrt_decay:
             tau = np.sqrt(tau)
         plan.run_dev(xp, dt, m.data_ptr() + (lo * nil * nxl * 4 if per_slice else 0), tau, niter, op, nb, active=active, mask_per_slice=per_slice, **common)
     return out

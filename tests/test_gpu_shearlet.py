@@ -569,8 +569,9 @@ def test_single_precision_cubes_take_the_double_loop_where_it_is_the_fused_one(s
     from pseudo_3d_interpolation_amd.functions import shearlets
     kw = dict(niter=6, thresh_op="soft", thresh_model="exponential", eps=0.0, p_max=0.99, p_min=1e-2)
     calls = []
-    real_double = P._pocs_cube_shearlet_double
-    monkeypatch.setattr(P, "_pocs_cube_shearlet_double", lambda *a, **k: (calls.append(a[0].shape), real_double(*a, **k))[1])
+    from pseudo_3d_interpolation_amd import _ffi
+    real_double = _ffi.ShearletPlan64.run_dev   # the run entry of the double-precision loop: recorded, then run
+    monkeypatch.setattr(_ffi.ShearletPlan64, "run_dev", lambda self, *a, **k: (calls.append((self.nil, self.nxl)), real_double(self, *a, **k))[1])
     for shape, expect in (((150, 240), True), ((128, 64), False), ((48, 40), False)):
         psi = shearlets.scalesShearsAndSpectra(shape)
         mask = po.synthetic_mask(shape[0], shape[1], 0.5)
