@@ -218,6 +218,42 @@ int p3d_pocs_dct_run(p3d_plan* plan, const void* x_host, int dtype, const float*
                      const p3d_pocs_params* params, void* out_host, int nslices, int32_t* niter_done, double* sums,
                      double* elapsed_ms, int norm);
 
+/* ---- windowed POCS: overlapping windows of every slice as independent jobs, blended by a tapered overlap-add (csrc/p3d_patch.hip) ------------
+ * A slice of nil x nxl points is cut into n_il x n_xl windows of the slice shape of `plan` (w_il x w_xl); window p = a * n_xl + b starts at
+ * (starts_il[a], starts_xl[b]) and window p of slice s is job s * npatch + p, npatch = n_il * n_xl.  Every job is one POCS job of its own
+ * (statistics, schedule, early exit, iteration count); the result is out[s][i][j] = sum_k W_k y_k / sum_k W_k over the active windows k covering
+ * (i, j) in ascending window order, W_k = taper_il[i - start_il] * taper_xl[j - start_xl], 0 where there is none.  float32 kernels: complex64 /
+ * float32 cubes.  A patch plan borrows `plan` (not owned; it must outlive the patch plan and hold max_slices * npatch slices), runs on its stream
+ * and is as little re-entrant.
+ *   create   starts_* HOST int32, strictly increasing with start + w <= extent; taper_* HOST float32 [w_il] / [w_xl], positive and finite;
+ *            anything else is P3D_ERR_INVALID
+ *   info     windows per slice, jobs the plan holds, and whether the single-kernel loop covers the window shape (extents of 32, 64, 128 with at
+ *            most 8192 points)
+ *   gather   cube_dev [nslices][nil][nxl] -> patches_dev [nslices * npatch][w_il][w_xl], dtype as given
+ *   mask     the windows of mask_dev -- [nil][nxl] with mask_slices = 1, [nslices][nil][nxl] with mask_slices = nslices -- packed for the
+ *            single-kernel loop (kept in the patch plan: npatch resp. nslices * npatch masks) and, where windows_dev is not NULL, as float32
+ *            [nslices * npatch][w_il][w_xl], one per job, the mask the plan's own loops take with P3D_FLAG_MASK_PER_SLICE; *nonbinary (may be
+ *            NULL) = 1 when a weight is neither 0 nor 1
+ *   route    *single_kernel = 1 when p3d_patch_run_dev takes the job: window shape covered, binary masks in the last p3d_patch_mask_dev, P3D_OP_HARD /
+ *            _SOFT / _GARROTE, P3D_VER_REGULAR / _FAST, and the environment variable P3D_NO_PATCH_RESIDENT unset (read at every call).  Every other job
+ *            runs p3d_pocs_run_dev / p3d_pocs_dct_run_dev of `plan` on the patch cube with windows_dev and P3D_FLAG_MASK_PER_SLICE.
+ *   run      the whole loop of every job in ONE kernel, a workgroup per job, with the masks of the last p3d_patch_mask_dev; arguments as
+ *            p3d_pocs_run_dev with nslices * npatch jobs in place of slices (tau [jobs][niter][2], active / niter_done [jobs], sums
+ *            [niter + 1][jobs]); results are bit for bit those of p3d_pocs_run_dev on window p's jobs with window p's mask.  P3D_ERR_UNSUPPORTED for
+ *            a job p3d_patch_route does not give it
+ *   blend    patches_dev (results) -> out_dev [nslices][nil][nxl]; active HOST [nslices * npatch] uint8 or NULL: 0 = the window contributes nothing */
+typedef struct p3d_patch_plan p3d_patch_plan;
+int p3d_patch_plan_create(p3d_patch_plan** out, p3d_plan* plan, int nil, int nxl, const int32_t* starts_il, int n_il, const int32_t* starts_xl,
+                          int n_xl, const float* taper_il, const float* taper_xl, int max_slices);
+int p3d_patch_plan_destroy(p3d_patch_plan* pplan);
+int p3d_patch_plan_info(p3d_patch_plan* pplan, int* npatch, int* max_jobs, int* resident_shape);
+int p3d_patch_gather_dev(p3d_patch_plan* pplan, const void* cube_dev, int dtype, int nslices, void* patches_dev);
+int p3d_patch_mask_dev(p3d_patch_plan* pplan, const float* mask_dev, int mask_slices, int nslices, float* windows_dev, int* nonbinary);
+int p3d_patch_route(p3d_patch_plan* pplan, const p3d_pocs_params* params, int* single_kernel);
+int p3d_patch_run_dev(p3d_patch_plan* pplan, const void* patches_dev, int dtype, const double* tau, const uint8_t* active,
+                      const p3d_pocs_params* params, void* out_dev, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms);
+int p3d_patch_blend_dev(p3d_patch_plan* pplan, const void* patches_dev, int dtype, const uint8_t* active, void* out_dev, int nslices);
+
 /* The same loop in the REFERENCE's precision.  POCS_algorithm computes in complex128 / float64 whenever its input is, under NumPy < 2 for every
  * input, and under NumPy >= 2 for the soft / garrote operators, FPOCS and APOCS on complex64 / float32 input as well (threshold_operator.py:37-39,
  * 76-78; POCS.py:566-575, 616: tau, the momentum scalar and the weights 1 - alpha * mask are float64 / complex128).  A plan64 runs

@@ -103,6 +103,16 @@ PROTOTYPES = {
     "p3d_pocs_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(PocsParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                C.POINTER(C.c_double)]),
+    "p3d_patch_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_int]),
+    "p3d_patch_plan_destroy": (C.c_int, [C.c_void_p]),
+    "p3d_patch_plan_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "p3d_patch_gather_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_patch_mask_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "p3d_patch_route": (C.c_int, [C.c_void_p, C.POINTER(PocsParams), C.POINTER(C.c_int)]),
+    "p3d_patch_run_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.POINTER(C.c_double)]),
+    "p3d_patch_blend_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "p3d_multi_stats": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "p3d_multi_run": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.POINTER(PocsParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -789,6 +799,85 @@ class Plan(_PlanBase):
         check(lib().p3d_last_profile(self.handle, C.byref(cm), C.byref(cn), C.byref(rm), C.byref(rn)))
         return {"colpass_ms": cm.value, "colpass_launches": cn.value, "rowpass_ms": rm.value,
                 "rowpass_launches": rn.value}
+
+
+class PatchPlan:
+    """p3d_patch_plan wrapper: the windows of (nil, nxl) slices over a ``Plan`` of the window shape that holds ``max_slices * npatch`` jobs (borrowed: the
+    plan must stay open).  ``starts_*``: the window starts per axis, ``taper_*``: the blend's taper per axis (float32 on the device).  Window ``p = a * n_xl + b``
+    of slice ``s`` is job ``s * npatch + p``.
+
+    ``test_hook`` (class attribute, None by default): a callable ``hook(windows, done, active)`` that ``functions.POCS.pocs_cube`` calls for every batch of a
+    windowed job with the UN-BLENDED window results (``(njobs, w_il, w_xl)``, downloaded for the purpose), the iterations of every window and its activity."""
+    test_hook = None
+
+    def __init__(self, plan, nil, nxl, starts_il, starts_xl, taper_il, taper_xl, max_slices):
+        self.plan, self.nil, self.nxl, self.max_slices = plan, int(nil), int(nxl), int(max_slices)
+        si, sx = (np.ascontiguousarray(s, dtype=np.int32) for s in (starts_il, starts_xl))
+        ti, tx = (np.ascontiguousarray(t, dtype=np.float32) for t in (taper_il, taper_xl))
+        if ti.shape != (plan.nil,) or tx.shape != (plan.nxl,):
+            raise ValueError(f"tapers of {ti.shape[0]} and {tx.shape[0]} points for windows of {plan.nil} x {plan.nxl}")
+        self.npatch = si.size * sx.size
+        self.handle = None
+        h = C.c_void_p()
+        check(lib().p3d_patch_plan_create(C.byref(h), plan.handle, self.nil, self.nxl, _ptr(si), si.size, _ptr(sx), sx.size, _ptr(ti), _ptr(tx), self.max_slices))
+        self.handle = h
+        n, jobs, res = C.c_int(), C.c_int(), C.c_int()
+        check(lib().p3d_patch_plan_info(self.handle, C.byref(n), C.byref(jobs), C.byref(res)))
+        assert n.value == self.npatch
+        self.max_jobs, self.resident_shape = jobs.value, bool(res.value)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().p3d_patch_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        if lib is not None:
+            self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def gather_dev(self, cube_ptr, dtype, nslices, patches_ptr):
+        """cube (device, [nslices][nil][nxl]) -> patch cube (device, [nslices * npatch][w_il][w_xl])."""
+        check(lib().p3d_patch_gather_dev(self.handle, cube_ptr, dtype, int(nslices), patches_ptr))
+
+    def mask_dev(self, mask_ptr, mask_slices, nslices, windows_ptr=None):
+        """Pack the windows of the float32 mask on the device (``mask_slices`` 1: shared, ``nslices``: one per slice) for `run_dev`; with ``windows_ptr``
+        also one float32 mask window per job, for the plan's own loops.  Returns True when a weight is neither 0 nor 1."""
+        odd = C.c_int(0)
+        check(lib().p3d_patch_mask_dev(self.handle, mask_ptr, int(mask_slices), int(nslices), windows_ptr, C.byref(odd)))
+        return bool(odd.value)
+
+    def route(self, thresh_op="hard", version="regular"):
+        """True when `run_dev` (the single-kernel loop) takes such a job with the masks of the last `mask_dev`."""
+        if thresh_op not in P3D_OP:
+            return False
+        one = C.c_int(0)
+        prm = Plan._params(1, thresh_op, version, 0.0, 1.0, False)
+        check(lib().p3d_patch_route(self.handle, C.byref(prm), C.byref(one)))
+        return bool(one.value)
+
+    def run_dev(self, patches_ptr, dtype, tau, niter, out_ptr, nslices, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
+        """The loop of every window of ``nslices`` slices in one kernel.  tau: broadcasts to (nslices * npatch, niter).  Returns (niter_done, sums, device ms)."""
+        n = int(nslices) * self.npatch
+        t = _tau_table(tau, (n, niter))
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
+        done = np.zeros(n, np.int32)
+        sums = np.zeros((niter + 1, n), np.float64)
+        ms = C.c_double(0.0)
+        check(lib().p3d_patch_run_dev(self.handle, patches_ptr, dtype, _ptr(t), None if act is None else _ptr(act), C.byref(prm), out_ptr, int(nslices), _ptr(done),
+                                      _ptr(sums), C.byref(ms)))
+        return done, sums, ms.value
+
+    def blend_dev(self, patches_ptr, dtype, active, out_ptr, nslices):
+        """Window results (device) -> blended cube (device, [nslices][nil][nxl]); ``active``: one flag per job (None: all)."""
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+        check(lib().p3d_patch_blend_dev(self.handle, patches_ptr, dtype, None if act is None else _ptr(act), out_ptr, int(nslices)))
 
 
 # ---- WAVELET variant -----------------------------------------------------------------------

@@ -1262,6 +1262,9 @@ struct RunJob {
     bool percentile;
     RunSwitches sw;
     LoopFrame frame;
+    const uint16_t* job_bits = nullptr;   // run_resident: one packed mask per job (resident_run_jobs) instead of the plan's packed mask ...
+    int job_period = 0;                   // ... job j reads job_bits + (j % job_period) * job_stride
+    size_t job_stride = 0;
 };
 
 // unfused any-length pipeline: first input, then per iteration fft2 -> threshold -> ifft2 -> re-insertion
@@ -1329,7 +1332,12 @@ static int run_resident(RunJob& j)
     ra.tw_row = p->tw_row; ra.tw_col = p->tw_col;
     ra.nslices = nslices; ra.niter = niter; ra.op = base_op; ra.dtype = dtype;
     ra.alpha = (float)prm->alpha; ra.scale = (float)(1.0 / ((double)p->nil * (double)p->nxl)); ra.eps = prm->eps;
-    P3D_TRY(resident_launch(p->nil, p->nxl, ra, p->stream));
+    if (j.job_bits) {
+        ra.bits = j.job_bits; ra.mask_period = j.job_period; ra.bits_stride = j.job_stride;
+        P3D_TRY(resident_patch_launch(p->nil, p->nxl, ra, p->stream));
+    } else {
+        P3D_TRY(resident_launch(p->nil, p->nxl, ra, p->stream));
+    }
     if ((rc = j.frame.enqueue_end(j.sums)) || (rc = j.frame.collect(j.niter_done, j.elapsed_ms))) return rc;
     p->last_nonzero_fraction = -1.0;
     p->prof_col_n = p->prof_row_n = 0;
@@ -1726,6 +1734,52 @@ int p3d_pocs_run_dev(p3d_plan* p, const void* x, int dtype, const float* mask, c
         return run_resident(j);
     return run_fused(j, nonbinary, nobs, primed_in, primed_state);
 }
+
+}  // extern "C"
+
+namespace p3d {
+
+static bool resident_shape(const p3d_plan* p)
+{
+    return !p->generic && !is_flex(p->ops_row) && !is_flex(p->ops_col) && resident_supported(p->nil, p->nxl) && (size_t)p->nil * p->nxl <= RESIDENT_MAX_POINTS;
+}
+
+void plan_describe(p3d_plan* p, int* device, int* nil, int* nxl, int* max_slices, int* single_kernel)
+{
+    *device = p->device; *nil = p->nil; *nxl = p->nxl; *max_slices = p->max_slices;
+    *single_kernel = resident_shape(p) ? 1 : 0;
+}
+
+// the front of p3d_pocs_run_dev (checks, schedule, state, clock) for jobs that bring one packed mask each, then run_resident
+int resident_run_jobs(p3d_plan* p, const void* x, int dtype, const uint16_t* bits, int mask_period, size_t bits_stride, const double* tau, const uint8_t* active,
+                      const p3d_pocs_params* prm, void* out, int njobs, int32_t* niter_done, double* sums, double* elapsed_ms)
+{
+    int rc = check_batch(p, njobs);
+    if (rc) return rc;
+    if (!x || !bits || !tau || !prm || !out) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (dtype != P3D_C64 && dtype != P3D_F32) return fail(P3D_ERR_INVALID, "unknown dtype %d", dtype);
+    if (prm->niter < 1) return fail(P3D_ERR_INVALID, "niter must be >= 1");
+    if (mask_period < 1) return fail(P3D_ERR_INVALID, "mask_period must be >= 1");
+    if (prm->thresh_op < P3D_OP_HARD || prm->thresh_op > P3D_OP_GARROTE || prm->version == P3D_VER_ADAPTIVE || !resident_shape(p))
+        return fail(P3D_ERR_UNSUPPORTED, "the single-kernel loop covers hard / soft / garrote, POCS / FPOCS and slices of 32 ... 128 points per axis, at most %d in all",
+                    (int)RESIDENT_MAX_POINTS);
+    if (prm->version < P3D_VER_REGULAR || prm->version > P3D_VER_ADAPTIVE) return fail(P3D_ERR_INVALID, "unknown version %d", prm->version);
+    P3D_TRY(hipSetDevice(p->device));
+    const int niter = prm->niter;
+    const size_t ntau = (size_t)njobs * niter;
+    if ((rc = grow(p->tau, p->tau_cap, ntau)) || (rc = grow(p->sums, p->sums_cap, (size_t)(niter + 1) * njobs))) return rc;
+    std::vector<c32> tau_f(ntau);
+    for (size_t i = 0; i < ntau; ++i) tau_f[i] = tau_for_device(tau[2 * i], tau[2 * i + 1], prm->thresh_op == P3D_OP_HARD);
+    RunJob j{p, x, dtype, nullptr, 0, tau, prm, out, njobs, niter_done, sums, elapsed_ms, prm->thresh_op, false, read_switches(), LoopFrame(p, active, njobs, niter)};
+    j.job_bits = bits; j.job_period = mask_period; j.job_stride = bits_stride;
+    P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
+    if ((rc = j.frame.begin())) return rc;
+    return run_resident(j);   // (synchronises the stream: tau_f has been read)
+}
+
+}  // namespace p3d
+
+extern "C" {
 
 int p3d_pocs_run(p3d_plan* p, const void* x, int dtype, const float* mask, const double* tau, const uint8_t* active,
                  const p3d_pocs_params* prm, void* out, int nslices, int32_t* niter_done, double* sums,

@@ -36,6 +36,14 @@ void set_last_error(const char* msg);
 // the stream all launches of a plan go to
 hipStream_t plan_stream(p3d_plan* plan);
 
+// ---- what the windowed loop (p3d_patch.hip) borrows from the plan of its window shape ------------------------------------------------------
+// device, slice shape and batch of a plan; single_kernel: the single-kernel loop (p3d_resident.hip) covers the shape on this plan
+void plan_describe(p3d_plan* plan, int* device, int* nil, int* nxl, int* max_slices, int* single_kernel);
+// p3d_pocs_run_dev on the single-kernel loop with one packed mask per job: job j reads the words at bits + (j % mask_period) * bits_stride (device, the
+// layout of ResidentArgs::bits).  hard / soft / garrote, POCS / FPOCS; every other argument as p3d_pocs_run_dev takes it.
+int resident_run_jobs(p3d_plan* plan, const void* x, int dtype, const uint16_t* bits, int mask_period, size_t bits_stride, const double* tau, const uint8_t* active,
+                      const p3d_pocs_params* prm, void* out, int njobs, int32_t* niter_done, double* sums, double* elapsed_ms);
+
 // p3d_fft2_c64_dev without the trailing stream synchronisation: batched 2-D FFT of complex64 slices on device buffers,
 // numpy.fft conventions, in == out allowed; enqueued on plan_stream(plan)
 int fft2_async(p3d_plan* plan, const c32* in, c32* out, int nslices, int inverse);

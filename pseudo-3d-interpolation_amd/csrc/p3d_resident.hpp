@@ -19,9 +19,13 @@ struct ResidentArgs {
     int nslices, niter, op, dtype;
     float alpha, scale;     // scale = 1 / (nil nxl)
     double eps;
+    int mask_period = 0;        // 0: one packed mask for the batch; > 0 (the windowed jobs of p3d_patch.hip): job j reads its words at
+    size_t bits_stride = 0;     //    bits + (j % mask_period) * bits_stride
 };
 
 bool resident_supported(int nil, int nxl);   // 32, 64 or 128 points per axis
 hipError_t resident_launch(int nil, int nxl, const ResidentArgs& a, hipStream_t st);
+// the same loop with one packed mask per job (a.mask_period > 0; p3d_patch.hip): the shapes of resident_supported up to 8192 points
+hipError_t resident_patch_launch(int nil, int nxl, const ResidentArgs& a, hipStream_t st);
 
 }  // namespace p3d

@@ -10,6 +10,8 @@ per-batch ``slice-XXXX-YYYY.out`` runtime files merged into ``runtimes_<prefix>.
 (:346-367).  Cubes are ``.npz`` files (cube_io.py) or netCDF when xarray is installed.  ``transform_kind``: FFT, WAVELET (with the ``wavelet`` key, default
 coif5, :261), SHEARLET (spectra from functions/shearlets.py instead of FFST, :269-272) or DCT (not in the reference's driver: scipy.fft.dctn / idctn of type 2,
 the optional ``dct_norm`` key -- ``ortho`` when absent, or ``backward`` -- joins the output prefix like the wavelet's name); the other kinds raise as the reference does when their third-party package is missing (:287-288).
+Optional ``patch_shape`` / ``patch_overlap`` / ``patch_taper`` keys of the ``metadata`` block (not in the reference's driver either) select windowed POCS and add
+``_patch-<w_il>x<w_xl>`` to the output prefix.
 """
 import argparse
 import datetime
@@ -155,6 +157,10 @@ def main(argv=sys.argv, return_dataset=False):
         metadata['transform'] = metadata['itransform'] = None
     else:
         raise ValueError(f'Transform < {metadata["transform_kind"]} > is not supported.')
+    if metadata.get('patch_shape') is not None:              # an extension: windowed POCS; patch_overlap / patch_taper travel with it in `metadata`
+        w = metadata['patch_shape']
+        w_il, w_xl = (int(w), int(w)) if np.ndim(w) == 0 else (int(w[0]), int(w[1]))
+        prefix += f'_patch-{w_il}x{w_xl}'
 
     coord = np.asarray(cube.coords[dim])
     step = int(cfg['batch_chunk'])

@@ -782,6 +782,9 @@ def pocs_cube(
     precision=None,
     out=None,
     dct_norm=None,
+    patch_shape=None,
+    patch_overlap=None,
+    patch_taper='hann',
     **ignored,
 ):
     """
@@ -822,11 +825,30 @@ def pocs_cube(
     ``out`` (optional): an array of the shape and dtype of ``cube`` to write the result into (e.g. a slab of the merged cube of the
     step-13 driver) instead of a new one.
 
+    ``patch_shape`` (``(w_il, w_xl)`` or one int; default None: every slice is one job, as ever) -- windowed POCS: every slice is cut into overlapping
+    windows (``patch_overlap``: ``(o_il, o_xl)`` or one int, default ``w // 2``; starts per axis from :func:`patch_starts`, all windows inside the slice), window
+    ``p`` of slice ``s`` is the independent job ``POCS_algorithm(cube[s, window], mask[window] or mask[s, window], ...)`` with its own statistics, schedule,
+    early exit and iteration count, a window whose samples are all zero contributes nothing, and the results are blended with the separable taper
+    ``patch_taper`` (``'hann'`` or ``'boxcar'``, :func:`patch_taper`): ``out = sum_k W_k y_k / sum_k W_k`` over the active windows covering a point, in ascending
+    window order, 0 where there is none.  FFT and DCT on the float32 kernels (WAVELET, SHEARLET and the double-precision loops raise ``NotImplementedError``).
+    Windows of 32, 64 or 128 points per axis (at most 8192 in all) with a binary mask, hard / soft / garrote, POCS / FPOCS and a statistics-driven schedule run
+    their whole loop in one kernel, a workgroup per window; everything else runs the unfused passes on the patch cube ("Windowed POCS").  Each dict
+    of ``results`` then holds the slice's ``niterations`` (the maximum over its active windows), ``cost`` (the maximum of the windows' final costs), ``costs``
+    (per iteration the maximum over the windows that executed it), ``runtime`` and ``patches``: ``(niterations, cost)`` per window, in window order.
+
     Returns an array with the shape and dtype of ``cube`` (``out`` when given).
     """
     cube, mask, kind, niter, eps, p_max, alpha, p_min = _check_cube_args(cube, mask, transform_kind, thresh_op, version, niter, eps,
                                                                          p_max, alpha, p_min)
     job = _Job(niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version)
+    geom = None
+    if patch_shape is not None:   # windowed POCS: the geometry and everything that cannot run, before anything is uploaded
+        geom = _patch_geometry(cube.shape[1:], patch_shape, patch_overlap, patch_taper)
+        if kind in ('WAVELET', 'SHEARLET'):
+            raise NotImplementedError(f'patch_shape is not implemented for the {kind} transform (FFT and DCT on the float32 kernels)')
+        if _double_loop_wanted(cube.dtype, cube.shape[1], cube.shape[2], kind, thresh_op, precision)[1]:
+            raise NotImplementedError("patch_shape is not implemented for the double-precision loops (precision='reference', or a complex128 / float64 cube "
+                                      "without precision='float32')")
     if out is None:
         out = np.empty_like(cube)
     elif not isinstance(out, np.ndarray) or out.shape != cube.shape or out.dtype != cube.dtype:
@@ -841,7 +863,154 @@ def pocs_cube(
     # device + stream"): calls on ONE device take turns -- a threaded caller (dask's threaded scheduler under xr.apply_ufunc) gets the same
     # results as a serial one; calls on different devices run side by side.
     with _device_lock(device):
+        if geom is not None:
+            return _pocs_cube_patched(cube, mask, kind, job, results, device, batch_slices, out, dct_norm, geom)
         return _pocs_cube_locked(cube, mask, kind, job, results, device, batch_slices, wavelet, auxiliary_data, precision, out, ignored, dct_norm)
+
+
+# =================================================================================================
+#                                      windowed POCS
+# =================================================================================================
+_PATCH_TAPERS = ('hann', 'boxcar')
+_PATCH_CUBE_BYTES = 1 << 30   # the patch cube of a batch stays below this unless the caller sets batch_slices
+
+
+def patch_starts(n, w, o):
+    """Window starts along an axis of ``n`` points for windows of ``w`` points that overlap by ``o``: ``0, step, 2 step, ...`` (``step = w - o``) while
+    ``start + w < n``, then one last window at ``n - w`` -- every window lies inside the axis, nothing is padded, the last one may overlap its neighbour by
+    more than ``o``.  ``n == w`` gives ``[0]``."""
+    n, w, o = int(n), int(w), int(o)
+    if w < 1 or w > n:
+        raise ValueError(f'a window of {w} points does not fit an axis of {n}')
+    if o < 0 or o >= w:
+        raise ValueError(f'overlap {o} outside 0 ... {w - 1} (window of {w} points)')
+    return list(range(0, n - w, w - o)) + [n - w]
+
+
+def patch_taper(w, kind='hann'):
+    """The blend's weights along one axis of a window of ``w`` points, float64: ``'hann'``: ``0.5 - 0.5 cos(2 pi (i + 0.5) / w)`` (strictly positive: the
+    samples sit at the half points), ``'boxcar'``: ones."""
+    if kind not in _PATCH_TAPERS:
+        raise ValueError(f'Unknown patch_taper {kind!r}. Please select one of: {_PATCH_TAPERS}')
+    if kind == 'boxcar':
+        return np.ones(int(w), np.float64)
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * (np.arange(int(w), dtype=np.float64) + 0.5) / int(w))
+
+
+_taper_table = patch_taper   # (``pocs_cube`` has a keyword argument of the function's name)
+
+
+def _patch_geometry(shape2d, patch_shape, patch_overlap, taper):
+    """``((w_il, w_xl), (starts_il, starts_xl), (taper_il, taper_xl))`` of a windowed job on ``(nil, nxl)`` slices; raises ValueError for what does not fit."""
+    def pair(v, what):
+        v = tuple(int(q) for q in v) if np.ndim(v) else (int(v), int(v))
+        if len(v) != 2:
+            raise ValueError(f'{what} must be one int or (iline, xline), got {v!r}')
+        return v
+    w = pair(patch_shape, 'patch_shape')
+    o = tuple(q // 2 for q in w) if patch_overlap is None else pair(patch_overlap, 'patch_overlap')
+    starts = tuple(patch_starts(n, wq, oq) for n, wq, oq in zip(shape2d, w, o))
+    return w, starts, tuple(_taper_table(wq, taper) for wq in w)
+
+
+def _patch_rows(done, sums, runtime, npatch):
+    """``_result_rows`` of a batch of windowed jobs folded per slice: the maxima over the slice's windows, and ``patches``: (niterations, cost) per window."""
+    rows = _result_rows(done, sums, runtime * npatch)   # (runtime per slice, not per window)
+    out = []
+    for s in range(len(rows) // npatch):
+        win = rows[s * npatch:(s + 1) * npatch]
+        k = max(r['niterations'] for r in win)
+        live = [r for r in win if r['niterations']]
+        out.append({
+            'niterations': k,
+            'runtime': win[0]['runtime'] if k else 0,
+            'cost': max(r['cost'] for r in live) if live else 0,
+            'costs': [max(r['costs'][i] for r in live if r['niterations'] > i) for i in range(k)] if k else [0],
+            'patches': [(r['niterations'], r['cost']) for r in win],
+        })
+    return out
+
+
+def _pocs_cube_patched(cube, mask, kind, job, results, device, batch_slices, out, dct_norm, geom):
+    """``pocs_cube`` with ``patch_shape``, the device's lock held: per batch one upload, gather -> per-window schedules -> the loop of every window -> blend,
+    one download.  The loop is the single-kernel one where ``_ffi.PatchPlan.route`` gives it the job, else the plan's own on the patch cube with one
+    materialised mask window per job."""
+    (w_il, w_xl), (s_il, s_xl), (t_il, t_xl) = geom
+    nslices, nil, nxl = cube.shape
+    npatch = len(s_il) * len(s_xl)
+    esz = 8 if np.iscomplexobj(cube) else 4
+    if batch_slices:
+        step = int(batch_slices)
+    else:
+        step = max(1, _PATCH_CUBE_BYTES // (npatch * w_il * w_xl * esz))
+    if npatch > 65535:
+        raise ValueError(f'{npatch} windows per slice: a plan holds at most 65535 jobs (larger windows or less overlap)')
+    step = max(1, min(step, nslices, 65535 // npatch))   # (a plan's limit: 65535 slices)
+    plan = _get_plan(w_il, w_xl, step * npatch, device, slot=13)
+    key = ('patch', nil, nxl, w_il, w_xl, tuple(s_il), tuple(s_xl), t_il.tobytes(), t_xl.tobytes(), device)
+    pp = _plans.get(key)
+    if pp is None or pp.plan is not plan or pp.plan.handle is None or pp.max_slices < step:
+        if pp is not None:
+            pp.close()
+        pp = _plans[key] = _ffi.PatchPlan(plan, nil, nxl, s_il, s_xl, t_il, t_xl, step)
+    maskf = np.ascontiguousarray(mask, dtype=np.float32)
+    per_slice = maskf.ndim == 3
+    data_driven = kind == 'FFT' and job.thresh_model == 'data-driven'
+    tau_of_batch = _tau_of_batch(kind, job, w_il, w_xl, dct_norm)
+    generic_run = partial(plan.dct_run_dev, norm=dct_norm) if kind == 'DCT' else plan.run_dev
+    wins = [(a, b) for a in s_il for b in s_xl]
+    njobs_max = step * npatch
+    bufs = [plan.alloc(step * nil * nxl * esz), plan.alloc(step * nil * nxl * esz), plan.alloc(njobs_max * w_il * w_xl * esz),
+            plan.alloc(njobs_max * w_il * w_xl * esz), plan.alloc(_mask_bytes(maskf, step))]
+    xd, od, pd, qd, md = bufs
+    try:
+        if not per_slice:
+            md.upload(maskf)
+        for lo in range(0, nslices, step):
+            chunk = cube[lo:lo + step]
+            n = chunk.shape[0]
+            njobs = n * npatch
+            t0 = time.perf_counter()
+            xc = np.ascontiguousarray(chunk, dtype=np.complex64 if esz == 8 else np.float32)
+            dt = _ffi.P3D_C64 if esz == 8 else _ffi.P3D_F32
+            xd.upload(xc)
+            if per_slice:
+                md.upload(maskf[lo:lo + n])
+            # a window whose samples are all zero is handed back untouched (POCS.py:515-521) and takes no part in the blend
+            active = np.stack([chunk[:, a:a + w_il, b:b + w_xl].reshape(n, -1).any(axis=1) for a, b in wins], axis=1).reshape(njobs)
+            pp.gather_dev(xd.ptr, dt, n, pd.ptr)
+            pp.mask_dev(md.ptr, n if per_slice else 1, n)
+            one_kernel = kind == 'FFT' and not data_driven and pp.route(job.thresh_op, job.version)
+            if not one_kernel:   # one materialised mask window per job, for the plan's own loop
+                if len(bufs) == 5:
+                    bufs.append(plan.alloc(njobs_max * w_il * w_xl * 4))
+                pp.mask_dev(md.ptr, n if per_slice else 1, n, bufs[5].ptr)
+            host = None
+            if data_driven and (dt != _ffi.P3D_C64 or isinstance(job.p_min, str)):   # (those picks sort a host copy of the batch)
+                host = pd.download((njobs, w_il, w_xl), xc.dtype)
+            tau = tau_of_batch(plan, host if host is not None else np.empty((njobs, 0, 0), xc.dtype), pd.ptr, dt, njobs, active)
+            if job.sqrt_decay:
+                tau = np.sqrt(tau)  # POCS.py:595
+            if one_kernel:
+                done, sums, _ = pp.run_dev(pd.ptr, dt, tau, job.niter, qd.ptr, n, thresh_op=job.thresh_op, version=job.version, eps=job.eps, alpha=job.alpha,
+                                           active=active)
+            else:
+                done, sums, _ = generic_run(pd.ptr, dt, bufs[5].ptr, tau, job.niter, qd.ptr, njobs, thresh_op=job.thresh_op, version=job.version, eps=job.eps,
+                                            alpha=job.alpha, active=active, mask_per_slice=True)
+            if _ffi.PatchPlan.test_hook is not None:
+                _ffi.PatchPlan.test_hook(qd.download((njobs, w_il, w_xl), xc.dtype), done.copy(), active.copy())
+            pp.blend_dev(qd.ptr, dt, active, od.ptr, n)
+            dst = out[lo:lo + n]
+            if dst.dtype == xc.dtype and dst.flags.c_contiguous:
+                od.download_into(dst)
+            else:
+                dst[...] = od.download(xc.shape, xc.dtype)
+            if results is not None:
+                results.extend(_patch_rows(done, sums, time.perf_counter() - t0, npatch))
+    finally:
+        for b in bufs:
+            b.free()
+    return out
 
 
 def _double_loop_wanted(dtype, nil, nxl, kind, thresh_op, precision, wavelet=None, transform=None, auxiliary_data=None):
