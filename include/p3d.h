@@ -241,6 +241,10 @@ int p3d_pocs_dct_run(p3d_plan* plan, const void* x_host, int dtype, const float*
  *            p3d_pocs_run_dev with nslices * npatch jobs in place of slices (tau [jobs][niter][2], active / niter_done [jobs], sums
  *            [niter + 1][jobs]); results are bit for bit those of p3d_pocs_run_dev on window p's jobs with window p's mask.  P3D_ERR_UNSUPPORTED for
  *            a job p3d_patch_route does not give it
+ *   dct_route / dct_run   the same two with scipy.fft.dctn / idctn (type 2, norm P3D_DCT_BACKWARD / P3D_DCT_ORTHO) as the transform of every window: the
+ *            single-kernel DCT loop (csrc/p3d_resident_dct_job.hpp) takes the jobs p3d_patch_route gives the FFT loop, for a norm it knows; tau is the
+ *            schedule of the windows' DCT spectra (p3d_pocs_dct_stats_dev on the patch cube).  Results agree with p3d_pocs_dct_run_dev on the patch cube
+ *            to float32 rounding, not bit for bit (another FFT, another summation order).  P3D_ERR_UNSUPPORTED for a job dct_route does not give it
  *   blend    patches_dev (results) -> out_dev [nslices][nil][nxl]; active HOST [nslices * npatch] uint8 or NULL: 0 = the window contributes nothing */
 typedef struct p3d_patch_plan p3d_patch_plan;
 int p3d_patch_plan_create(p3d_patch_plan** out, p3d_plan* plan, int nil, int nxl, const int32_t* starts_il, int n_il, const int32_t* starts_xl,
@@ -252,6 +256,9 @@ int p3d_patch_mask_dev(p3d_patch_plan* pplan, const float* mask_dev, int mask_sl
 int p3d_patch_route(p3d_patch_plan* pplan, const p3d_pocs_params* params, int* single_kernel);
 int p3d_patch_run_dev(p3d_patch_plan* pplan, const void* patches_dev, int dtype, const double* tau, const uint8_t* active,
                       const p3d_pocs_params* params, void* out_dev, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms);
+int p3d_patch_dct_route(p3d_patch_plan* pplan, const p3d_pocs_params* params, int norm, int* single_kernel);
+int p3d_patch_dct_run_dev(p3d_patch_plan* pplan, const void* patches_dev, int dtype, const double* tau, const uint8_t* active,
+                          const p3d_pocs_params* params, int norm, void* out_dev, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms);
 int p3d_patch_blend_dev(p3d_patch_plan* pplan, const void* patches_dev, int dtype, const uint8_t* active, void* out_dev, int nslices);
 
 /* The same loop in the REFERENCE's precision.  POCS_algorithm computes in complex128 / float64 whenever its input is, under NumPy < 2 for every

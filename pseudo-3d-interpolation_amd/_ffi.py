@@ -112,6 +112,9 @@ PROTOTYPES = {
     "p3d_patch_route": (C.c_int, [C.c_void_p, C.POINTER(PocsParams), C.POINTER(C.c_int)]),
     "p3d_patch_run_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_int, C.c_void_p,
                                     C.c_void_p, C.POINTER(C.c_double)]),
+    "p3d_patch_dct_route": (C.c_int, [C.c_void_p, C.POINTER(PocsParams), C.c_int, C.POINTER(C.c_int)]),
+    "p3d_patch_dct_run_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.POINTER(C.c_double)]),
     "p3d_patch_blend_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "p3d_multi_stats": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "p3d_multi_run": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -852,13 +855,19 @@ class PatchPlan:
         check(lib().p3d_patch_mask_dev(self.handle, mask_ptr, int(mask_slices), int(nslices), windows_ptr, C.byref(odd)))
         return bool(odd.value)
 
-    def route(self, thresh_op="hard", version="regular"):
-        """True when `run_dev` (the single-kernel loop) takes such a job with the masks of the last `mask_dev`."""
-        if thresh_op not in P3D_OP:
+    def route(self, thresh_op="hard", version="regular", transform="FFT", norm=None):
+        """True when `run_dev` (the single-kernel loop; ``transform='DCT'``: `dct_run_dev` with the DCT pair of ``norm``) takes such a job with the masks of
+        the last `mask_dev`."""
+        if thresh_op not in P3D_OP or transform not in ("FFT", "DCT"):
             return False
         one = C.c_int(0)
         prm = Plan._params(1, thresh_op, version, 0.0, 1.0, False)
-        check(lib().p3d_patch_route(self.handle, C.byref(prm), C.byref(one)))
+        if transform == "DCT":
+            if norm not in P3D_DCT_NORM:
+                return False
+            check(lib().p3d_patch_dct_route(self.handle, C.byref(prm), P3D_DCT_NORM[norm], C.byref(one)))
+        else:
+            check(lib().p3d_patch_route(self.handle, C.byref(prm), C.byref(one)))
         return bool(one.value)
 
     def run_dev(self, patches_ptr, dtype, tau, niter, out_ptr, nslices, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None):
@@ -872,6 +881,20 @@ class PatchPlan:
         ms = C.c_double(0.0)
         check(lib().p3d_patch_run_dev(self.handle, patches_ptr, dtype, _ptr(t), None if act is None else _ptr(act), C.byref(prm), out_ptr, int(nslices), _ptr(done),
                                       _ptr(sums), C.byref(ms)))
+        return done, sums, ms.value
+
+    def dct_run_dev(self, patches_ptr, dtype, tau, niter, out_ptr, nslices, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, active=None, norm=None):
+        """`run_dev` with scipy.fft.dctn / idctn (type 2, ``norm``) as the transform of every window: the single-kernel DCT loop.  tau: the schedule of the
+        windows' DCT spectra.  Returns (niter_done, sums, device ms)."""
+        n = int(nslices) * self.npatch
+        t = _tau_table(tau, (n, niter))
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+        prm = Plan._params(niter, thresh_op, version, eps, alpha, False)
+        done = np.zeros(n, np.int32)
+        sums = np.zeros((niter + 1, n), np.float64)
+        ms = C.c_double(0.0)
+        check(lib().p3d_patch_dct_run_dev(self.handle, patches_ptr, dtype, _ptr(t), None if act is None else _ptr(act), C.byref(prm), Plan._dct_norm(norm), out_ptr,
+                                          int(nslices), _ptr(done), _ptr(sums), C.byref(ms)))
         return done, sums, ms.value
 
     def blend_dev(self, patches_ptr, dtype, active, out_ptr, nslices):

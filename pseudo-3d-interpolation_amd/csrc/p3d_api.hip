@@ -20,6 +20,7 @@
 #include "p3d_flex.hpp"
 #include "p3d_mix_entry.hpp"
 #include "p3d_resident.hpp"
+#include "p3d_resident_dct.hpp"
 #include "p3d_select.hpp"
 #include "p3d_kernels.hpp"
 
@@ -1265,6 +1266,7 @@ struct RunJob {
     const uint16_t* job_bits = nullptr;   // run_resident: one packed mask per job (resident_run_jobs) instead of the plan's packed mask ...
     int job_period = 0;                   // ... job j reads job_bits + (j % job_period) * job_stride
     size_t job_stride = 0;
+    const c32* dct_fac = nullptr;         // ... and, with job_bits, the DCT loop of the windowed jobs (p3d_patch_dct.hip) on these factors (one norm of p3d_plan::dct_tab)
 };
 
 // unfused any-length pipeline: first input, then per iteration fft2 -> threshold -> ifft2 -> re-insertion
@@ -1334,7 +1336,8 @@ static int run_resident(RunJob& j)
     ra.alpha = (float)prm->alpha; ra.scale = (float)(1.0 / ((double)p->nil * (double)p->nxl)); ra.eps = prm->eps;
     if (j.job_bits) {
         ra.bits = j.job_bits; ra.mask_period = j.job_period; ra.bits_stride = j.job_stride;
-        P3D_TRY(resident_patch_launch(p->nil, p->nxl, ra, p->stream));
+        if (j.dct_fac) P3D_TRY(resident_dct_patch_launch(p->nil, p->nxl, ResidentDctArgs{ra, j.dct_fac}, p->stream));
+        else P3D_TRY(resident_patch_launch(p->nil, p->nxl, ra, p->stream));
     } else {
         P3D_TRY(resident_launch(p->nil, p->nxl, ra, p->stream));
     }
@@ -1750,9 +1753,25 @@ void plan_describe(p3d_plan* p, int* device, int* nil, int* nxl, int* max_slices
     *single_kernel = resident_shape(p) ? 1 : 0;
 }
 
-// the front of p3d_pocs_run_dev (checks, schedule, state, clock) for jobs that bring one packed mask each, then run_resident
-int resident_run_jobs(p3d_plan* p, const void* x, int dtype, const uint16_t* bits, int mask_period, size_t bits_stride, const double* tau, const uint8_t* active,
-                      const p3d_pocs_params* prm, void* out, int njobs, int32_t* niter_done, double* sums, double* elapsed_ms)
+// the DCT factor tables of both norms (p3d_dct_tables.hpp), built on the first DCT call of a plan
+static int dct_ensure_tables(p3d_plan* p)
+{
+    if (p->dct_tab) return P3D_OK;
+    const size_t per = 2 * ((size_t)p->nil + p->nxl);
+    std::vector<c32> host(2 * per);
+    for (int norm = 0; norm < 2; ++norm) {
+        c32* b = host.data() + norm * per;
+        dct::build_tables(p->nil, norm, b, b + p->nil);
+        dct::build_tables(p->nxl, norm, b + 2 * (size_t)p->nil, b + 2 * (size_t)p->nil + p->nxl);
+    }
+    P3D_TRY(hipMalloc((void**)&p->dct_tab, sizeof(c32) * host.size()));
+    P3D_TRY(hipMemcpy(p->dct_tab, host.data(), sizeof(c32) * host.size(), hipMemcpyHostToDevice));
+    return P3D_OK;
+}
+
+// the front of p3d_pocs_run_dev (checks, schedule, state, clock) for jobs that bring one packed mask each, then run_resident; dct_norm < 0: the FFT loop
+static int run_jobs(p3d_plan* p, const void* x, int dtype, const uint16_t* bits, int mask_period, size_t bits_stride, const double* tau, const uint8_t* active,
+                    const p3d_pocs_params* prm, void* out, int njobs, int32_t* niter_done, double* sums, double* elapsed_ms, int dct_norm)
 {
     int rc = check_batch(p, njobs);
     if (rc) return rc;
@@ -1764,7 +1783,9 @@ int resident_run_jobs(p3d_plan* p, const void* x, int dtype, const uint16_t* bit
         return fail(P3D_ERR_UNSUPPORTED, "the single-kernel loop covers hard / soft / garrote, POCS / FPOCS and slices of 32 ... 128 points per axis, at most %d in all",
                     (int)RESIDENT_MAX_POINTS);
     if (prm->version < P3D_VER_REGULAR || prm->version > P3D_VER_ADAPTIVE) return fail(P3D_ERR_INVALID, "unknown version %d", prm->version);
+    if (dct_norm >= 0 && dct_norm != P3D_DCT_BACKWARD && dct_norm != P3D_DCT_ORTHO) return fail(P3D_ERR_UNSUPPORTED, "DCT norm %d is not implemented (backward, ortho)", dct_norm);
     P3D_TRY(hipSetDevice(p->device));
+    if (dct_norm >= 0 && (rc = dct_ensure_tables(p))) return rc;
     const int niter = prm->niter;
     const size_t ntau = (size_t)njobs * niter;
     if ((rc = grow(p->tau, p->tau_cap, ntau)) || (rc = grow(p->sums, p->sums_cap, (size_t)(niter + 1) * njobs))) return rc;
@@ -1772,9 +1793,23 @@ int resident_run_jobs(p3d_plan* p, const void* x, int dtype, const uint16_t* bit
     for (size_t i = 0; i < ntau; ++i) tau_f[i] = tau_for_device(tau[2 * i], tau[2 * i + 1], prm->thresh_op == P3D_OP_HARD);
     RunJob j{p, x, dtype, nullptr, 0, tau, prm, out, njobs, niter_done, sums, elapsed_ms, prm->thresh_op, false, read_switches(), LoopFrame(p, active, njobs, niter)};
     j.job_bits = bits; j.job_period = mask_period; j.job_stride = bits_stride;
+    if (dct_norm >= 0) j.dct_fac = p->dct_tab + (size_t)dct_norm * 2 * ((size_t)p->nil + p->nxl);
     P3D_TRY(hipMemcpyAsync(p->tau, tau_f.data(), sizeof(c32) * ntau, hipMemcpyHostToDevice, p->stream));
     if ((rc = j.frame.begin())) return rc;
     return run_resident(j);   // (synchronises the stream: tau_f has been read)
+}
+
+int resident_run_jobs(p3d_plan* p, const void* x, int dtype, const uint16_t* bits, int mask_period, size_t bits_stride, const double* tau, const uint8_t* active,
+                      const p3d_pocs_params* prm, void* out, int njobs, int32_t* niter_done, double* sums, double* elapsed_ms)
+{
+    return run_jobs(p, x, dtype, bits, mask_period, bits_stride, tau, active, prm, out, njobs, niter_done, sums, elapsed_ms, -1);
+}
+
+int resident_dct_run_jobs(p3d_plan* p, const void* x, int dtype, const uint16_t* bits, int mask_period, size_t bits_stride, const double* tau, const uint8_t* active,
+                          const p3d_pocs_params* prm, void* out, int njobs, int32_t* niter_done, double* sums, double* elapsed_ms, int norm)
+{
+    if (norm < 0) return fail(P3D_ERR_UNSUPPORTED, "DCT norm %d is not implemented (backward, ortho)", norm);
+    return run_jobs(p, x, dtype, bits, mask_period, bits_stride, tau, active, prm, out, njobs, niter_done, sums, elapsed_ms, norm);
 }
 
 }  // namespace p3d
@@ -1812,17 +1847,7 @@ static int dct_ensure(p3d_plan* p)
         P3D_TRY(hipMalloc((void**)&p->dct_w, sizeof(c32) * n));
         P3D_TRY(hipMemsetAsync(p->dct_w, 0, sizeof(c32) * n, p->stream));   // (slices a job switches off are transformed all the same: keep them finite)
     }
-    if (!p->dct_tab) {
-        const size_t per = 2 * ((size_t)p->nil + p->nxl);
-        std::vector<c32> host(2 * per);
-        for (int norm = 0; norm < 2; ++norm) {
-            c32* b = host.data() + norm * per;
-            dct::build_tables(p->nil, norm, b, b + p->nil);
-            dct::build_tables(p->nxl, norm, b + 2 * (size_t)p->nil, b + 2 * (size_t)p->nil + p->nxl);
-        }
-        P3D_TRY(hipMalloc((void**)&p->dct_tab, sizeof(c32) * host.size()));
-        P3D_TRY(hipMemcpy(p->dct_tab, host.data(), sizeof(c32) * host.size(), hipMemcpyHostToDevice));
-    }
+    if (int rc = dct_ensure_tables(p)) return rc;
     if (!p->pct_sel) P3D_TRY(hipMalloc((void**)&p->pct_sel, sizeof(unsigned) * 16 * ms));
     if (!p->pct_hist) P3D_TRY(hipMalloc((void**)&p->pct_hist, sizeof(unsigned) * 2048 * ms));
     if (!p->pct_frac) P3D_TRY(hipMalloc((void**)&p->pct_frac, sizeof(float) * ms));

@@ -43,6 +43,10 @@ void plan_describe(p3d_plan* plan, int* device, int* nil, int* nxl, int* max_sli
 // layout of ResidentArgs::bits).  hard / soft / garrote, POCS / FPOCS; every other argument as p3d_pocs_run_dev takes it.
 int resident_run_jobs(p3d_plan* plan, const void* x, int dtype, const uint16_t* bits, int mask_period, size_t bits_stride, const double* tau, const uint8_t* active,
                       const p3d_pocs_params* prm, void* out, int njobs, int32_t* niter_done, double* sums, double* elapsed_ms);
+// the same with scipy.fft.dctn / idctn (type 2, norm P3D_DCT_BACKWARD / P3D_DCT_ORTHO) as the transform: the single-kernel DCT loop of p3d_patch_dct.hip on the
+// plan's DCT factor tables (built here on first use); tau is the schedule of the DCT spectrum (p3d_pocs_dct_stats_dev)
+int resident_dct_run_jobs(p3d_plan* plan, const void* x, int dtype, const uint16_t* bits, int mask_period, size_t bits_stride, const double* tau, const uint8_t* active,
+                          const p3d_pocs_params* prm, void* out, int njobs, int32_t* niter_done, double* sums, double* elapsed_ms, int norm);
 
 // p3d_fft2_c64_dev without the trailing stream synchronisation: batched 2-D FFT of complex64 slices on device buffers,
 // numpy.fft conventions, in == out allowed; enqueued on plan_stream(plan)

@@ -6,6 +6,7 @@
 //
 //     cube [n][nil][nxl]  --patch_gather_kernel-->  patch cube [n npatch][w_il][w_xl]                     (8 + 8 B per patch point, complex64)
 //     mask                --patch_pack_kernel-->    packed words of the single-kernel loop, one mask per window (resident_kernel<.., op | RESIDENT_MASK_PER_JOB>)
+//                                                   (DCT windows: resident_dct_kernel of p3d_patch_dct.hip on the same words, p3d_patch_dct_run_dev below)
 //     patch results       --patch_blend_kernel-->   out [n][nil][nxl] = sum_k W_k y_k / sum_k W_k            (8 B per covering window + 8 B per point)
 //
 // All three are bound by memory: one element per thread, consecutive threads on consecutive xline positions (coalesced 8-byte / 4-byte accesses; window starts
@@ -365,6 +366,34 @@ int p3d_patch_run_dev(p3d_patch_plan* pp, const void* patches, int dtype, const 
         return fail(P3D_ERR_INVALID, "the packed masks are those of another batch (%d windows, this one has %d per slice x %d slices)", pp->packed_period, npatch, nslices);
     return resident_run_jobs(pp->plan, patches, dtype, pp->bits, pp->packed_period, (size_t)pp->g.w_il * (pp->g.w_xl / 16), tau, active, params, out, nslices * npatch,
                              niter_done, sums, elapsed_ms);
+}
+
+// the DCT loop's route: the jobs of one_kernel() with a norm the factor tables have
+static bool one_kernel_dct(const p3d_patch_plan* pp, const p3d_pocs_params* prm, int norm)
+{
+    return (norm == P3D_DCT_BACKWARD || norm == P3D_DCT_ORTHO) && one_kernel(pp, prm);
+}
+
+int p3d_patch_dct_route(p3d_patch_plan* pp, const p3d_pocs_params* params, int norm, int* single_kernel)
+{
+    if (!pp || !params || !single_kernel) return fail(P3D_ERR_INVALID, "NULL argument");
+    *single_kernel = one_kernel_dct(pp, params, norm) ? 1 : 0;
+    return P3D_OK;
+}
+
+int p3d_patch_dct_run_dev(p3d_patch_plan* pp, const void* patches, int dtype, const double* tau, const uint8_t* active, const p3d_pocs_params* params, int norm,
+                          void* out, int nslices, int32_t* niter_done, double* sums, double* elapsed_ms)
+{
+    if (int rc = check_slices(pp, nslices)) return rc;
+    if (!params) return fail(P3D_ERR_INVALID, "NULL argument");
+    if (!one_kernel_dct(pp, params, norm))
+        return fail(P3D_ERR_UNSUPPORTED, "the single-kernel windowed DCT loop does not cover this job (window shape, operator, version, norm, non-binary masks, or "
+                                         "P3D_NO_PATCH_RESIDENT): run p3d_pocs_dct_run_dev on the patch cube with P3D_FLAG_MASK_PER_SLICE");
+    const int npatch = pp->g.n_il * pp->g.n_xl;
+    if (pp->packed_period != npatch && pp->packed_period != nslices * npatch)
+        return fail(P3D_ERR_INVALID, "the packed masks are those of another batch (%d windows, this one has %d per slice x %d slices)", pp->packed_period, npatch, nslices);
+    return resident_dct_run_jobs(pp->plan, patches, dtype, pp->bits, pp->packed_period, (size_t)pp->g.w_il * (pp->g.w_xl / 16), tau, active, params, out,
+                                 nslices * npatch, niter_done, sums, elapsed_ms, norm);
 }
 
 int p3d_patch_blend_dev(p3d_patch_plan* pp, const void* patches, int dtype, const uint8_t* active, void* out, int nslices)

@@ -933,7 +933,7 @@ def _patch_rows(done, sums, runtime, npatch):
 
 def _pocs_cube_patched(cube, mask, kind, job, results, device, batch_slices, out, dct_norm, geom):
     """``pocs_cube`` with ``patch_shape``, the device's lock held: per batch one upload, gather -> per-window schedules -> the loop of every window -> blend,
-    one download.  The loop is the single-kernel one where ``_ffi.PatchPlan.route`` gives it the job, else the plan's own on the patch cube with one
+    one download.  The loop is the single-kernel one (FFT or DCT) where ``_ffi.PatchPlan.route`` gives it the job, else the plan's own on the patch cube with one
     materialised mask window per job."""
     (w_il, w_xl), (s_il, s_xl), (t_il, t_xl) = geom
     nslices, nil, nxl = cube.shape
@@ -980,7 +980,10 @@ def _pocs_cube_patched(cube, mask, kind, job, results, device, batch_slices, out
             active = np.stack([chunk[:, a:a + w_il, b:b + w_xl].reshape(n, -1).any(axis=1) for a, b in wins], axis=1).reshape(njobs)
             pp.gather_dev(xd.ptr, dt, n, pd.ptr)
             pp.mask_dev(md.ptr, n if per_slice else 1, n)
-            one_kernel = kind == 'FFT' and not data_driven and pp.route(job.thresh_op, job.version)
+            if kind == 'DCT':
+                one_kernel = pp.route(job.thresh_op, job.version, transform='DCT', norm=dct_norm)
+            else:
+                one_kernel = kind == 'FFT' and not data_driven and pp.route(job.thresh_op, job.version)
             if not one_kernel:   # one materialised mask window per job, for the plan's own loop
                 if len(bufs) == 5:
                     bufs.append(plan.alloc(njobs_max * w_il * w_xl * 4))
@@ -992,8 +995,9 @@ def _pocs_cube_patched(cube, mask, kind, job, results, device, batch_slices, out
             if job.sqrt_decay:
                 tau = np.sqrt(tau)  # POCS.py:595
             if one_kernel:
-                done, sums, _ = pp.run_dev(pd.ptr, dt, tau, job.niter, qd.ptr, n, thresh_op=job.thresh_op, version=job.version, eps=job.eps, alpha=job.alpha,
-                                           active=active)
+                resident_run = partial(pp.dct_run_dev, norm=dct_norm) if kind == 'DCT' else pp.run_dev
+                done, sums, _ = resident_run(pd.ptr, dt, tau, job.niter, qd.ptr, n, thresh_op=job.thresh_op, version=job.version, eps=job.eps, alpha=job.alpha,
+                                             active=active)
             else:
                 done, sums, _ = generic_run(pd.ptr, dt, bufs[5].ptr, tau, job.niter, qd.ptr, njobs, thresh_op=job.thresh_op, version=job.version, eps=job.eps,
                                             alpha=job.alpha, active=active, mask_per_slice=True)
