@@ -95,6 +95,8 @@ const char* p3d_last_error(void);
  * libamdhip64 was mapped first; the Python binding warns when major.minor disagree) */
 int p3d_runtime_info(int* compiled_hip_version, int* runtime_hip_version);
 int p3d_device_count(int* n);
+/* compute units of a device: the persistent passes run one or two workgroups on each (tests size their jobs by it) */
+int p3d_device_cus(int device, int* n);
 
 /* 1 when the HIP kernels cover an (nil, nxl) slice shape, else 0 */
 int p3d_shape_supported(int nil, int nxl);

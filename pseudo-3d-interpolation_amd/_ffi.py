@@ -47,6 +47,7 @@ PROTOTYPES = {
     "p3d_abi_version": (C.c_int, []),
     "p3d_last_error": (C.c_char_p, []),
     "p3d_device_count": (C.c_int, [C.POINTER(C.c_int)]),
+    "p3d_device_cus": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "p3d_shape_supported": (C.c_int, [C.c_int, C.c_int]),
     "p3d_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),
     "p3d_plan_destroy": (C.c_int, [C.c_void_p]),
@@ -310,6 +311,13 @@ def check(code):
 def device_count():
     n = C.c_int(0)
     check(lib().p3d_device_count(C.byref(n)))
+    return n.value
+
+
+def device_cus(device=0):
+    """Compute units of a device (the persistent row and column passes size their grids by it)."""
+    n = C.c_int(0)
+    check(lib().p3d_device_cus(int(device), C.byref(n)))
     return n.value
 
 

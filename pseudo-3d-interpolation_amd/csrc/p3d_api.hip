@@ -428,6 +428,14 @@ int p3d_device_count(int* n)
     return P3D_OK;
 }
 
+int p3d_device_cus(int device, int* n)
+{
+    if (!n) return fail(P3D_ERR_INVALID, "n is NULL");
+    *n = 0;
+    P3D_TRY(hipDeviceGetAttribute(n, hipDeviceAttributeMultiprocessorCount, device));
+    return P3D_OK;
+}
+
 static bool generic_ok(int n) { return n >= 1 && n <= GEN_MAX_N && gen_make_plan(n).nf >= 0; }
 
 int p3d_shape_supported(int nil, int nxl)

@@ -98,16 +98,95 @@ P3D_HD void p32_half1(c32 (&v)[32], c32* row, int j)
 #pragma unroll
     for (int m = 0; m < 32; ++m) p[m] = v[m];
 }
+//
+// The reads of the second half: v[0] = q[0], v[t] = q[34 t] * tw[32 (t - 1) + j] (times the conjugate for the inverse), q = row + j, then the
+// butterfly.  Written as that loop of plain loads the compiler requests a (value, twiddle) pair, waits for it, multiplies and only then requests
+// the next: thirty dependent trips to LDS per transform with one or two reads in flight, in a kernel that runs two wavefronts per SIMD
+// (measured: 1 - 1.7 % of the headline job, profiles/rowpass_batched_exchange.txt).  So the reads are issued here by hand, in four GROUPS of eight values and their
+// eight twiddles (eight ds_read2_b64), two groups ahead of the multiplications: sixteen reads are in flight before the first wait, and a
+// transform waits four times.  LDS reads of a wavefront return in order, so `lgkmcnt(8)` behind the request of group g + 1 says group g has
+// arrived (anything else the counter may still hold -- a scalar load from before -- only makes the wait longer).  The compiler does not know
+// what an asm statement has in flight: the wait takes the group's registers as in-out operands, so whatever uses them depends on the wait.
+// On the host the same grouping runs on plain loads (tests/csrc/test_fft32_batched_host.cpp compares it with that loop, bit for bit).
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef float p32_two __attribute__((ext_vector_type(4)));   // two complex values: what one ds_read2_b64 returns
+__device__ __forceinline__ c32 p32_lo(p32_two r) { return c32{r.x, r.y}; }
+__device__ __forceinline__ c32 p32_hi(p32_two r) { return c32{r.z, r.w}; }
+// base[A], base[B] (A, B < 256: the instruction's offsets count 8-byte units in eight bits)
+template <int A, int B>
+__device__ __forceinline__ p32_two p32_read2(const c32* base)
+{
+    static_assert(A >= 0 && A < 256 && B >= 0 && B < 256, "ds_read2_b64 offsets");
+    const unsigned addr = (unsigned)(size_t)(const __attribute__((address_space(3))) c32*)base;
+    p32_two r;
+    asm volatile("ds_read2_b64 %0, %1 offset0:%2 offset1:%3" : "=v"(r) : "v"(addr), "n"(A), "n"(B) : "memory");
+    return r;
+}
+// the eight reads of a group have arrived once at most LEFT younger ones are in flight
+template <int LEFT>
+__device__ __forceinline__ void p32_arrived(p32_two (&a)[4], p32_two (&w)[4])
+{
+    __builtin_amdgcn_sched_barrier(0);   // (the multiplications of the group before stay in front of this wait, under the reads just requested)
+    asm volatile("s_waitcnt lgkmcnt(%[left])"
+                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3])
+                 : [left] "n"(LEFT));
+}
+#else
+struct p32_two { c32 lo, hi; };
+inline c32 p32_lo(p32_two r) { return r.lo; }
+inline c32 p32_hi(p32_two r) { return r.hi; }
+template <int A, int B>
+inline p32_two p32_read2(const c32* base) { return p32_two{base[A], base[B]}; }
+template <int LEFT>
+inline void p32_arrived(p32_two (&)[4], p32_two (&)[4]) {}
+#endif
+// request group G: the values t = 8 G ... 8 G + 7 of lane j (q = row + j: value t at q[34 t]) and their twiddles (twj = tw + j: twiddle t at
+// twj[32 (t - 1)], t >= 1).  Pair i holds t = 8 G + 2 i and the one behind it; t = 0 has no twiddle, its slot takes a second copy of t = 1's.
+template <int G>
+P3D_HD void p32_request(p32_two (&a)[4], p32_two (&w)[4], const c32* q, const c32* twj)
+{
+    const c32* const qb = q + 34 * 8 * G;
+    const c32* const wb = twj + (G == 0 ? 0 : 32 * (8 * G - 1));
+    constexpr int D = G == 0 ? -32 : 0;
+    a[0] = p32_read2<0, 34>(qb);
+    a[1] = p32_read2<68, 102>(qb);
+    a[2] = p32_read2<136, 170>(qb);
+    a[3] = p32_read2<204, 238>(qb);
+    w[0] = p32_read2<(D < 0 ? 0 : D), 32 + D>(wb);
+    w[1] = p32_read2<64 + D, 96 + D>(wb);
+    w[2] = p32_read2<128 + D, 160 + D>(wb);
+    w[3] = p32_read2<192 + D, 224 + D>(wb);
+}
+// v[t] <- value * twiddle for the eight t of group G: the loop's operations, element by element
+template <int DIR, int G>
+P3D_HD void p32_twiddle(c32 (&v)[32], const p32_two (&a)[4], const p32_two (&w)[4])
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int t = 8 * G + 2 * i;
+        if (t == 0) v[0] = p32_lo(a[0]);
+        else v[t] = DIR > 0 ? mul_conj(p32_lo(a[i]), p32_lo(w[i])) : p32_lo(a[i]) * p32_lo(w[i]);
+        v[t + 1] = DIR > 0 ? mul_conj(p32_hi(a[i]), p32_hi(w[i])) : p32_hi(a[i]) * p32_hi(w[i]);
+    }
+}
 template <int DIR>
 P3D_HD void p32_half2(c32 (&v)[32], const c32* row, const c32* tw, int j)
 {
     const c32* const q = row + j;
-    v[0] = q[0];
-#pragma unroll
-    for (int t = 1; t < 32; ++t) {
-        const c32 w = tw[(t - 1) * 32 + j];
-        v[t] = DIR > 0 ? mul_conj(q[34 * t], w) : q[34 * t] * w;
-    }
+    const c32* const twj = tw + j;
+    p32_two a0[4], w0[4], a1[4], w1[4], a2[4], w2[4], a3[4], w3[4];
+    p32_request<0>(a0, w0, q, twj);
+    p32_request<1>(a1, w1, q, twj);
+    p32_arrived<8>(a0, w0);
+    p32_twiddle<DIR, 0>(v, a0, w0);
+    p32_request<2>(a2, w2, q, twj);
+    p32_arrived<8>(a1, w1);
+    p32_twiddle<DIR, 1>(v, a1, w1);
+    p32_request<3>(a3, w3, q, twj);
+    p32_arrived<8>(a2, w2);
+    p32_twiddle<DIR, 2>(v, a2, w2);
+    p32_arrived<0>(a3, w3);
+    p32_twiddle<DIR, 3>(v, a3, w3);
     dft32<DIR>(v);
 }
 
