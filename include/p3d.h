@@ -725,6 +725,43 @@ int p3d_merge_records_dev(int device, const unsigned char* records_dev, int nsrc
 int p3d_merge_records(int device, const unsigned char* records, int nsrc, int reclen, int nout, const int* src, const int* lo_row, const int* hi_row,
                       unsigned char* out);
 
+/* ---- 3-D FFT POCS: a whole volume as ONE job (csrc/p3d_vol.hip) ------------------------------------------------------------------------------
+ * POCS_algorithm(x, mask, transform=np.fft.fftn, itransform=np.fft.ifftn, transform_kind='FFT', ...) on a volume x of (n0, n1, n2) points,
+ * C-contiguous, n2 fastest: the spectrum couples all three axes, there is one schedule, one cost, one iteration count and one early exit for
+ * the volume.  Per iteration: the fft2 passes of a p3d_plan for (n1, n2) slices, one kernel that transforms a tile of plane positions along
+ * axis 0, thresholds and transforms back (the 3-D spectrum never goes to memory), the ifft2 passes, and the re-insertion with cost sums
+ * folded in a fixed order (results are bitwise repeatable).  float32 kernels: complex64 volumes, or float32 ones, which run as complex
+ * with a zero imaginary part and return the real part.
+ *   shape_supported  1 when n0 is a 7-smooth length from 1 to 1024 (n0 = 1: the axis-0 pass thresholds only) and p3d_shape_supported(n1, n2)
+ *   create   `plan`: a p3d_plan for (n1, n2) slices on `device` to borrow (not owned: it must outlive the volume plan, which runs on its stream
+ *            and is as little re-entrant), or NULL: the volume plan creates and owns one.  Allocates the complex64 work volume.
+ *            P3D_ERR_UNSUPPORTED for any other n0 or slice shape
+ *   fft3     np.fft.fftn (inverse = 0) / ifftn (inverse = 1) of one complex64 volume through the loop's own passes; test hook like p3d_fft2_c64;
+ *            in == out is allowed
+ *   shrink   threshold(fftn(x), tau, thresh_op), tau HOST [2] doubles (Re, Im): the keep / zero decision of every coefficient (test hook)
+ *   stats    stats_host [P3D_STATS_PER_SLICE] of X0 = fftn(x), the layout of p3d_pocs_stats for ONE volume
+ *   run      the loop.  x, out [n0][n1][n2] of `dtype` (P3D_C64 / P3D_F32); mask float32 [n1][n2], or [n0][n1][n2] with P3D_FLAG_MASK_PER_SLICE
+ *            in params->flags; tau HOST [niter][2] doubles; niter_done HOST, one int32; sums HOST [niter + 1] doubles or NULL (sum |x_k|, 0 where
+ *            not executed); elapsed_ms device time of the call or NULL.  hard / soft / garrote, every version, eps and alpha of p3d_pocs_params
+ *            (P3D_FLAG_PRIMED is ignored; P3D_FLAG_PROFILE brackets every axis-0 pass with HIP events, read with p3d_vol_last_profile: mean device
+ *            milliseconds of that kernel in the last run and its launches).  An all-zero volume comes back untouched with niter_done = 0.  A device `out` that
+ *            overlaps `x` is written through a staging volume (every iteration reads x).
+ * The *_dev entries take DEVICE pointers for x, mask and out, the others HOST pointers (staged through volumes the plan allocates on first use). */
+typedef struct p3d_vol_plan p3d_vol_plan;
+int p3d_vol_shape_supported(int n0, int n1, int n2);
+int p3d_vol_plan_create(p3d_vol_plan** out, int device, int n0, int n1, int n2, p3d_plan* plan);
+int p3d_vol_plan_destroy(p3d_vol_plan* vplan);
+int p3d_vol_fft3_c64_dev(p3d_vol_plan* vplan, const void* in_dev, void* out_dev, int inverse);
+int p3d_vol_fft3_c64(p3d_vol_plan* vplan, const void* in_host, void* out_host, int inverse);
+int p3d_vol_shrink_c64(p3d_vol_plan* vplan, const void* in_host, const double* tau, int thresh_op, void* out_host);
+int p3d_vol_last_profile(p3d_vol_plan* vplan, double* zpass_ms, int* zpass_launches);
+int p3d_vol_stats_dev(p3d_vol_plan* vplan, const void* x_dev, int dtype, double* stats_host);
+int p3d_vol_stats(p3d_vol_plan* vplan, const void* x_host, int dtype, double* stats_host);
+int p3d_vol_run_dev(p3d_vol_plan* vplan, const void* x_dev, int dtype, const float* mask_dev, const double* tau, const p3d_pocs_params* params, void* out_dev,
+                    int32_t* niter_done, double* sums, double* elapsed_ms);
+int p3d_vol_run(p3d_vol_plan* vplan, const void* x_host, int dtype, const float* mask_host, const double* tau, const p3d_pocs_params* params, void* out_host,
+                int32_t* niter_done, double* sums, double* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,9 @@ per-batch ``slice-XXXX-YYYY.out`` runtime files merged into ``runtimes_<prefix>.
 coif5, :261), SHEARLET (spectra from functions/shearlets.py instead of FFST, :269-272) or DCT (not in the reference's driver: scipy.fft.dctn / idctn of type 2,
 the optional ``dct_norm`` key -- ``ortho`` when absent, or ``backward`` -- joins the output prefix like the wavelet's name); the other kinds raise as the reference does when their third-party package is missing (:287-288).
 Optional ``patch_shape`` / ``patch_overlap`` / ``patch_taper`` keys of the ``metadata`` block (not in the reference's driver either) select windowed POCS and add
-``_patch-<w_il>x<w_xl>`` to the output prefix.
+``_patch-<w_il>x<w_xl>`` to the output prefix.  Optional ``volume: true`` in the ``metadata`` block (an extension as well): the data variable, ``dim``
+first, runs as ONE 3-D FFT POCS job (``pocs_volume``: np.fft.fftn / ifftn over all three axes, one schedule and one early exit for the volume) with the fold mask or
+``mask_var`` (2-D, or 3-D with the data variable's dims); the prefix gains ``_vol`` and the runtime file holds one line.
 """
 import argparse
 import datetime
@@ -24,11 +26,12 @@ import numpy as np
 import yaml
 
 from .cube_io import open_cube, save_cube
-from .functions.POCS import APOCS, FPOCS, POCS, pocs_cube  # noqa: F401
+from .functions.POCS import APOCS, FPOCS, POCS, pocs_cube, pocs_volume  # noqa: F401
 from .functions.utils import xprint
 
 POCS_VERSIONS = {'POCS': POCS, 'FPOCS': FPOCS, 'APOCS': APOCS}
 ffloat = partial(np.format_float_positional, trim='-')
+VOLUME_KEYS = ('niter', 'thresh_op', 'thresh_model', 'eps', 'alpha', 'p_max', 'p_min', 'sqrt_decay', 'decay_kind', 'version', 'device')   # of `metadata`, for pocs_volume
 
 
 def define_input_args():  # noqa
@@ -88,6 +91,22 @@ def dct_norm_from_metadata(metadata):
     return norm
 
 
+def volume_from_metadata(metadata):
+    """The optional ``volume`` key of the YAML ``metadata`` block (3-D FFT POCS of the whole data variable as one job) and the combinations it excludes."""
+    volume = metadata.get('volume')
+    if volume is None or volume is False:
+        return False
+    if volume is not True:
+        raise ValueError(f'volume must be true or false, got {volume!r}')
+    if metadata.get('patch_shape') is not None:
+        raise NotImplementedError('volume: true cannot be combined with patch_shape (3-D windows are not implemented)')
+    if str(metadata['transform_kind']).upper() != 'FFT':
+        raise NotImplementedError(f"volume: true is implemented for transform_kind FFT only, got {metadata['transform_kind']}")
+    if metadata.get('precision') == 'reference':
+        raise NotImplementedError('volume: true cannot be combined with precision: reference (there is no double-precision volume loop)')
+    return True
+
+
 def main(argv=sys.argv, return_dataset=False):
     """Interpolate sparse 3D cube."""
     SCRIPT = os.path.basename(__file__)
@@ -101,6 +120,7 @@ def main(argv=sys.argv, return_dataset=False):
         cfg['metadata']['transform_kind'] = cfg['metadata']['transform_kind'].upper()
     metadata = cfg['metadata']
     TRANSFORM = metadata['transform_kind']
+    VOLUME = volume_from_metadata(metadata)                  # before anything is created or read
 
     path_cube = args.path_cube
     dir_work, file = os.path.split(path_cube)
@@ -161,6 +181,8 @@ def main(argv=sys.argv, return_dataset=False):
         w = metadata['patch_shape']
         w_il, w_xl = (int(w), int(w)) if np.ndim(w) == 0 else (int(w[0]), int(w[1]))
         prefix += f'_patch-{w_il}x{w_xl}'
+    if VOLUME:                                               # an extension: the whole data variable as one 3-D FFT POCS job
+        prefix += '_vol'
 
     coord = np.asarray(cube.coords[dim])
     step = int(cfg['batch_chunk'])
@@ -214,6 +236,17 @@ def main(argv=sys.argv, return_dataset=False):
         cur_bytes += nb
     if cur:
         groups.append(cur)
+    if VOLUME:
+        results = []
+        merged[...] = pocs_volume(data, mask, results=results, **{k: kwargs[k] for k in VOLUME_KEYS if k in kwargs})
+        for sl in batches:                                   # the output keeps its unit, one file per batch; the job has ONE runtime record
+            save_cube(wrap(merged[sl], sl), create_file_path(coord[sl], prefix=prefix, root_path=out_path, suffix=suffix))
+        if cfg.get('output_runtime_results'):
+            with open(os.path.join(out_path, f'slice-{0:04d}-{coord.size:04d}.out'), mode='a', newline='\n') as f:
+                info = results[0]
+                f.write(';'.join([str(i) for i in [info['niterations'], info['runtime']] + info['costs']]) + '\n')
+        xprint(f'volume {data.shape} done', kind='info', verbosity=verbose)
+        groups = []
     for group in groups:
         span = slice(group[0].start, group[-1].stop)
         results = []

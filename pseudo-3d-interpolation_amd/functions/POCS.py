@@ -1166,6 +1166,122 @@ def _pocs_cube_locked(cube, mask, kind, job, results, device, batch_slices, wave
 
 
 # =================================================================================================
+#                                      3-D FFT POCS: a whole volume as one job
+# =================================================================================================
+_VOL_MAX_N0 = 1024   # VOL_MAX_N0 of csrc/p3d_vol.hip
+
+
+def _vol_n0_supported(n):
+    """The axis-0 lengths of the volume kernels: 7-smooth, 1 ... 1024 (p3d_vol_shape_supported, evaluated here so that a refusal needs no library)."""
+    if not 1 <= n <= _VOL_MAX_N0:
+        return False
+    for r in (2, 3, 5, 7):
+        while n % r == 0:
+            n //= r
+    return n == 1
+
+
+def _vol_n0_neighbours(n):
+    """The nearest supported axis-0 lengths below and above ``n`` (None where there is none)."""
+    below = next((m for m in range(min(n - 1, _VOL_MAX_N0), 0, -1) if _vol_n0_supported(m)), None)
+    above = next((m for m in range(max(n + 1, 1), _VOL_MAX_N0 + 1) if _vol_n0_supported(m)), None)
+    return below, above
+
+
+def _vol_bytes_needed(shape, itemsize, mask_bytes):
+    """Device bytes of one ``pocs_volume`` job: the complex64 work volume, the observed volume and the result, the mask, and the 2-D plan's own buffers
+    (up to 256 MiB of slices, three such buffers at most)."""
+    n = int(np.prod(shape, dtype=np.int64))
+    plane = shape[1] * shape[2] * 8
+    slices = max(1, min(shape[0], (256 << 20) // plane))
+    return 8 * n + 2 * itemsize * n + mask_bytes + 3 * slices * plane
+
+
+def pocs_volume(x, mask, niter=50, thresh_op='hard', thresh_model='exponential', eps=1e-9, alpha=1.0, p_max=0.99, p_min=1e-5,
+                sqrt_decay=False, decay_kind='values', version='regular', device=0, results=None):
+    """
+    3-D FFT POCS of ONE volume: ``POCS_algorithm(x, mask, transform=np.fft.fftn, itransform=np.fft.ifftn, transform_kind='FFT', ...)`` of the
+    reference on a ``(n0, n1, n2)`` array (e.g. ``(twt, iline, xline)``) -- the sparse domain couples all three axes, and there is one threshold
+    schedule (from the statistics of ``fftn(x)``), one cost, one iteration count and one early exit for the whole volume.
+
+    ``x``: complex64 or float32 (float32 runs as complex with a zero imaginary part and returns the real part); ``mask``: ``(n1, n2)``, shared by every
+    ``x[i]``, or ``(n0, n1, n2)``; entries ``<= 1``, weights allowed.  ``n0``: a 7-smooth length from 1 to 1024, ``(n1, n2)``: any slice shape of
+    :func:`pocs_cube`.  hard / soft / garrote; every version; the statistics-driven threshold models.  ``results`` (list, optional) receives one dict
+    with ``niterations``, ``runtime``, ``cost`` and ``costs``.  Returns an array of the shape and dtype of ``x``; an all-zero volume comes back untouched.
+
+    The volume, its result and a complex64 work volume live on the device for the call (``MemoryError`` when they do not fit).
+    """
+    name = 'pocs_volume'
+    x = np.asarray(x)
+    if x.ndim != 3:
+        raise ValueError(f'{name}: x must be a (n0, n1, n2) volume, got shape {x.shape}')
+    mask = np.asarray(mask)
+    if mask.shape != x.shape[1:] and mask.shape != x.shape:
+        raise ValueError(f'{name}: mask shape {mask.shape} is neither {x.shape[1:]} nor {x.shape}')
+    if thresh_op not in _THRESH_OPS:
+        raise ValueError(f'{name}: unknown threshold operator {thresh_op!r}. Please select one of: {_THRESH_OPS}')
+    if 'percentile' in thresh_op:
+        raise NotImplementedError(f'{name}: the -percentile operators ({thresh_op!r}) are not implemented for volumes (hard, soft, garrote)')
+    if thresh_model == 'data-driven':
+        raise NotImplementedError(f"{name}: thresh_model='data-driven' is not implemented for volumes")
+    if x.dtype in (np.complex128, np.float64):
+        raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex64 / float32 volumes; there is no double-precision volume loop and '
+                                  'the input is not narrowed silently)')
+    if x.dtype not in (np.complex64, np.float32):
+        raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex64 / float32 volumes)')
+    if version not in _ffi.P3D_VER:
+        raise ValueError(f'{name}: unknown POCS version {version!r}')
+    if mask.size and np.max(mask) > 1:
+        raise ValueError(f'{name}: mask should be quasi-boolean (0 or 1) but has maximum of {np.max(mask)}')
+    niter, eps, p_max, alpha = int(niter), float(eps), float(p_max), float(alpha)
+    if isinstance(p_min, str) and p_min != 'adaptive':
+        p_min = float(p_min)
+    if niter < 1:
+        raise ValueError(f'{name}: niter must be >= 1')
+    n0, n1, n2 = x.shape
+    if not _vol_n0_supported(n0):
+        below, above = _vol_n0_neighbours(n0)
+        near = ' and '.join(f'{m} ({side})' for m, side in ((below, 'below'), (above, 'above')) if m is not None)
+        raise ValueError(f'{name}: n0 = {n0} is not supported along the first axis (7-smooth lengths from 1 to {_VOL_MAX_N0}); nearest supported: {near}')
+    if n1 < 1 or n2 < 1:
+        raise ValueError(f'{name}: empty volume of shape {x.shape}')
+
+    if not x.any():   # np.count_nonzero(x) == 0: handed back untouched (POCS.py:515-521)
+        if results is not None:
+            results.append({'niterations': 0, 'runtime': 0, 'cost': 0, 'costs': [0]})
+        return x.copy()
+
+    maskf = np.ascontiguousarray(mask, dtype=np.float32)
+    xc = np.ascontiguousarray(x)
+    dt = _ffi.P3D_C64 if np.iscomplexobj(xc) else _ffi.P3D_F32
+    with _device_lock(device):
+        if not _ffi.shape_supported(n1, n2):
+            raise ValueError(f'{name}: slice shape {(n1, n2)} is not covered by the HIP kernels')
+        key = ('vol', n0, n1, n2, device)
+        if key not in _plans:
+            needed = _vol_bytes_needed(x.shape, xc.itemsize, maskf.nbytes)
+            free, _ = _ffi.device_mem_info(device)
+            if needed > free:
+                raise MemoryError(f'{name}: a {x.shape} {x.dtype} volume needs {needed} bytes on device {device}, {free} are free')
+        t0 = time.perf_counter()
+        plan = _cached_plan(key, 1, lambda n: _ffi.VolumePlan(n0, n1, n2, device=device))
+        xd, od, md = _batch_buffers(device, xc.nbytes, maskf.nbytes)
+        xd.upload(xc)
+        md.upload(maskf)
+        stats = plan.stats_dev(xd.ptr, dt)
+        tau = _schedule_from_stats(stats, x.size, thresh_model, niter, p_max, p_min, decay_kind)[0]
+        if sqrt_decay:
+            tau = np.sqrt(tau)   # POCS.py:595
+        done, sums, _ = plan.run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha,
+                                     mask_per_slice=maskf.ndim == 3)
+        out = od.download(xc.shape, xc.dtype)
+        runtime = time.perf_counter() - t0
+    if results is not None:
+        results.extend(_result_rows(np.array([done]), sums[:, None], runtime))
+    return out
+
+
+# =================================================================================================
 #                                      per-slice contract
 # =================================================================================================
 _FFT_MODULES = ('numpy.fft', 'scipy.fft', 'scipy.fftpack', 'pyfftw.interfaces', 'mkl_fft')
