@@ -762,6 +762,37 @@ int p3d_vol_run_dev(p3d_vol_plan* vplan, const void* x_dev, int dtype, const flo
 int p3d_vol_run(p3d_vol_plan* vplan, const void* x_host, int dtype, const float* mask_host, const double* tau, const p3d_pocs_params* params, void* out_host,
                 int32_t* niter_done, double* sums, double* elapsed_ms);
 
+/* ---- 3-D FFT POCS in double precision (csrc/p3d_vol64.hip) -----------------------------------------------------------------------------------
+ * The volume loop above in the reference's own precision (POCS.py:566-575, 616: complex128 / float64 throughout): a complex128 work volume, the line
+ * passes of a p3d_plan64 for (n1, n2) slices, one axis-0 kernel on complex128 with NumPy's threshold semantics in double, a double mask, cost sums
+ * folded in a fixed order (no atomics: results are bitwise repeatable).  Within 1e-10 of the float64 oracle on every seeded case, none set aside.
+ *   shape_supported  1 when n0 is a 7-smooth length from 1 to 1024 and (n1, n2) is a slice shape p3d_plan64_create takes (extents up to 5120)
+ *   create   `plan`: a p3d_plan64 for (n1, n2) slices on `device` to borrow (not owned: it must outlive the volume plan, which runs on its stream
+ *            and is as little re-entrant), or NULL: the volume plan creates and owns one.  Allocates the complex128 work volume.
+ *            P3D_ERR_UNSUPPORTED for any other n0 or slice shape
+ *   fft3     np.fft.fftn (inverse = 0) / ifftn (inverse = 1) of one complex128 volume through the loop's own passes (test hook); in == out is allowed
+ *   shrink   threshold(fftn(x), tau, thresh_op) of a complex128 volume, tau HOST [2] doubles (Re, Im) (test hook)
+ *   stats    stats_host [P3D_STATS_PER_SLICE] of X0 = fftn(x), every reduction in double
+ *   run      the loop.  x, out [n0][n1][n2] of `dtype`: P3D_C128, P3D_F64, or P3D_C64 / P3D_F32 (converted on load / store; real volumes run as complex
+ *            with a zero imaginary part); mask DOUBLE [n1][n2], or [n0][n1][n2] with P3D_FLAG_MASK_PER_SLICE; tau, niter_done, sums, elapsed_ms, the
+ *            operators (hard / soft / garrote), versions, eps, alpha, P3D_FLAG_PROFILE (read with last_profile), the all-zero volume and an `out` that
+ *            overlaps `x` as in the float32 entries above.
+ * The *_dev entries take DEVICE pointers for x, mask and out, the others HOST pointers (staged through volumes the plan allocates on first use). */
+typedef struct p3d_vol64_plan p3d_vol64_plan;
+int p3d_vol64_shape_supported(int n0, int n1, int n2);
+int p3d_vol64_plan_create(p3d_vol64_plan** out, int device, int n0, int n1, int n2, p3d_plan64* plan);
+int p3d_vol64_plan_destroy(p3d_vol64_plan* vplan);
+int p3d_vol64_fft3_c128_dev(p3d_vol64_plan* vplan, const void* in_dev, void* out_dev, int inverse);
+int p3d_vol64_fft3_c128(p3d_vol64_plan* vplan, const void* in_host, void* out_host, int inverse);
+int p3d_vol64_shrink_c128(p3d_vol64_plan* vplan, const void* in_host, const double* tau, int thresh_op, void* out_host);
+int p3d_vol64_last_profile(p3d_vol64_plan* vplan, double* zpass_ms, int* zpass_launches);
+int p3d_vol64_stats_dev(p3d_vol64_plan* vplan, const void* x_dev, int dtype, double* stats_host);
+int p3d_vol64_stats(p3d_vol64_plan* vplan, const void* x_host, int dtype, double* stats_host);
+int p3d_vol64_run_dev(p3d_vol64_plan* vplan, const void* x_dev, int dtype, const double* mask_dev, const double* tau, const p3d_pocs_params* params, void* out_dev,
+                      int32_t* niter_done, double* sums, double* elapsed_ms);
+int p3d_vol64_run(p3d_vol64_plan* vplan, const void* x_host, int dtype, const double* mask_host, const double* tau, const p3d_pocs_params* params, void* out_host,
+                  int32_t* niter_done, double* sums, double* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

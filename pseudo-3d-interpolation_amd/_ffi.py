@@ -238,6 +238,19 @@ PROTOTYPES = {
                                   C.POINTER(C.c_double)]),
     "p3d_vol_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_void_p, C.c_void_p,
                               C.POINTER(C.c_double)]),
+    "p3d_vol64_shape_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "p3d_vol64_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_vol64_plan_destroy": (C.c_int, [C.c_void_p]),
+    "p3d_vol64_fft3_c128_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "p3d_vol64_fft3_c128": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "p3d_vol64_shrink_c128": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "p3d_vol64_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "p3d_vol64_stats_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "p3d_vol64_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "p3d_vol64_run_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_double)]),
+    "p3d_vol64_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.POINTER(C.c_double)]),
 }
 
 
@@ -932,6 +945,7 @@ class VolumePlan(_PlanBase):
     """p3d_vol_plan wrapper: 3-D FFT POCS of one ``(n0, n1, n2)`` volume (csrc/p3d_vol.hip).  ``plan``: a :class:`Plan` for ``(n1, n2)`` slices on the same
     device to borrow (kept alive here), or None: the volume plan owns one.  ``max_slices`` is 1: a volume is one job."""
     _DESTROY = "p3d_vol_plan_destroy"
+    _ENTRY, _HOOK = "p3d_vol_", "c64"        # the C entries are _ENTRY + name; the transform hooks end in _HOOK, the type they take
     max_slices = 1
 
     def __init__(self, n0, n1, n2, device=0, plan=None):
@@ -939,8 +953,11 @@ class VolumePlan(_PlanBase):
         self.shape = (self.n0, self.n1, self.n2)
         self.plan = plan
         h = C.c_void_p()
-        check(lib().p3d_vol_plan_create(C.byref(h), self.device, self.n0, self.n1, self.n2, None if plan is None else plan.handle))
+        check(self._c("plan_create")(C.byref(h), self.device, self.n0, self.n1, self.n2, None if plan is None else plan.handle))
         self.handle = h
+
+    def _c(self, name):
+        return getattr(lib(), self._ENTRY + name)
 
     def _volume(self, x, complex_only=False):
         x = np.asarray(x)
@@ -954,30 +971,30 @@ class VolumePlan(_PlanBase):
         """np.fft.fftn (``inverse``: ifftn) of a complex64 volume through the loop's own passes."""
         xc, _ = self._volume(x, complex_only=True)
         out = np.empty_like(xc)
-        check(lib().p3d_vol_fft3_c64(self.handle, _ptr(xc), _ptr(out), int(bool(inverse))))
+        check(self._c("fft3_" + self._HOOK)(self.handle, _ptr(xc), _ptr(out), int(bool(inverse))))
         return out
 
     def fft3_dev(self, in_ptr, out_ptr, inverse=False):
-        check(lib().p3d_vol_fft3_c64_dev(self.handle, C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(bool(inverse))))
+        check(self._c("fft3_" + self._HOOK + "_dev")(self.handle, C.c_void_p(in_ptr), C.c_void_p(out_ptr), int(bool(inverse))))
 
     def shrink(self, x, tau, thresh_op="hard"):
         """threshold(fftn(x), tau, kind) on the device: the keep / zero decision of every coefficient."""
         xc, _ = self._volume(x, complex_only=True)
         t = _tau_table(tau, ())
         out = np.empty_like(xc)
-        check(lib().p3d_vol_shrink_c64(self.handle, _ptr(xc), _ptr(t), P3D_OP[thresh_op], _ptr(out)))
+        check(self._c("shrink_" + self._HOOK)(self.handle, _ptr(xc), _ptr(t), P3D_OP[thresh_op], _ptr(out)))
         return out
 
     def stats(self, x):
         """The six statistics of ``fftn(x)`` as a (1, 6) array (one row: the volume), the layout ``_schedule_from_stats`` takes."""
         xc, dt = self._volume(x)
         st = np.empty((1, STATS_PER_SLICE), np.float64)
-        check(lib().p3d_vol_stats(self.handle, _ptr(xc), dt, _ptr(st)))
+        check(self._c("stats")(self.handle, _ptr(xc), dt, _ptr(st)))
         return st
 
     def stats_dev(self, x_ptr, dtype):
         st = np.empty((1, STATS_PER_SLICE), np.float64)
-        check(lib().p3d_vol_stats_dev(self.handle, C.c_void_p(x_ptr), int(dtype), _ptr(st)))
+        check(self._c("stats_dev")(self.handle, C.c_void_p(x_ptr), int(dtype), _ptr(st)))
         return st
 
     def _run(self, entry, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, thresh_op, version, eps, alpha, mask_per_slice, profile=False):
@@ -988,32 +1005,55 @@ class VolumePlan(_PlanBase):
         done = np.zeros(1, np.int32)
         sums = np.zeros(int(niter) + 1, np.float64)
         ms = C.c_double(0.0)
-        check(getattr(lib(), entry)(self.handle, C.c_void_p(x_ptr), int(dtype), C.c_void_p(mask_ptr), _ptr(t), C.byref(prm), C.c_void_p(out_ptr), _ptr(done),
-                                    _ptr(sums), C.byref(ms)))
+        check(self._c(entry)(self.handle, C.c_void_p(x_ptr), int(dtype), C.c_void_p(mask_ptr), _ptr(t), C.byref(prm), C.c_void_p(out_ptr), _ptr(done),
+                             _ptr(sums), C.byref(ms)))
         return int(done[0]), sums, ms.value
 
     def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0):
         """Host arrays in, host array out; ``mask`` (n1, n2) or (n0, n1, n2); ``tau``: (niter,), real or complex.  Returns (out, niter_done, sums,
         elapsed_ms) with sums[k] = sum |x_k| over the volume."""
         xc, dt = self._volume(x)
-        m = np.ascontiguousarray(mask, dtype=np.float32)
+        m = np.ascontiguousarray(mask, dtype=self._MASK_DT)
         if m.shape != self.shape[1:] and m.shape != self.shape:
             raise ValueError(f"mask shape {m.shape} is neither {self.shape[1:]} nor {self.shape}")
         out = np.empty_like(xc)
-        done, sums, ms = self._run("p3d_vol_run", xc.ctypes.data, dt, m.ctypes.data, tau, niter, out.ctypes.data, thresh_op, version, eps, alpha, m.ndim == 3)
+        done, sums, ms = self._run("run", xc.ctypes.data, dt, m.ctypes.data, tau, niter, out.ctypes.data, thresh_op, version, eps, alpha, m.ndim == 3)
         return out, done, sums, ms
 
     def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, mask_per_slice=False,
                 profile=False):
         """`run` on device pointers (``out_ptr`` may be ``x_ptr``); ``profile``: time every axis-0 pass (`last_profile`).  Returns (niter_done, sums,
         elapsed_ms)."""
-        return self._run("p3d_vol_run_dev", x_ptr, dtype, mask_ptr, tau, niter, out_ptr, thresh_op, version, eps, alpha, mask_per_slice, profile)
+        return self._run("run_dev", x_ptr, dtype, mask_ptr, tau, niter, out_ptr, thresh_op, version, eps, alpha, mask_per_slice, profile)
 
     def last_profile(self):
         """After a run with ``profile=True``: mean device milliseconds of the axis-0 pass and its launches."""
         ms, n = C.c_double(), C.c_int()
-        check(lib().p3d_vol_last_profile(self.handle, C.byref(ms), C.byref(n)))
+        check(self._c("last_profile")(self.handle, C.byref(ms), C.byref(n)))
         return {"zpass_ms": ms.value, "zpass_launches": n.value}
+
+
+def vol64_shape_supported(n0, n1, n2):
+    return bool(lib().p3d_vol64_shape_supported(int(n0), int(n1), int(n2)))
+
+
+class VolumePlan64(VolumePlan):
+    """p3d_vol64_plan wrapper: the volume loop in double precision (csrc/p3d_vol64.hip) with the methods of :class:`VolumePlan`.  Volumes of complex128,
+    float64, complex64 and float32 go in as they are (anything else is widened) and come back in their own type; the arithmetic is double, the mask
+    float64, the transform hooks take complex128.  ``plan``: a :class:`Plan64` for ``(n1, n2)`` slices to borrow, or None."""
+    _DESTROY = "p3d_vol64_plan_destroy"
+    _ENTRY, _HOOK = "p3d_vol64_", "c128"
+    _MASK_DT = np.float64
+
+    def _volume(self, x, complex_only=False):
+        x = np.asarray(x)
+        if x.shape != self.shape:
+            raise ValueError(f"expected a volume of shape {self.shape}, got {x.shape}")
+        if complex_only:
+            return np.ascontiguousarray(x, dtype=np.complex128), P3D_C128
+        if x.dtype not in _PlanBase64._DT:
+            x = x.astype(np.complex128 if np.iscomplexobj(x) else np.float64)
+        return np.ascontiguousarray(x), _PlanBase64._DT[x.dtype]
 
 
 # ---- WAVELET variant -----------------------------------------------------------------------

@@ -1155,6 +1155,10 @@ namespace p3d {
 int plan64_create_bare(p3d_plan64** out, int device, int nil, int nxl, int max_slices) { return create64(out, device, nil, nxl, max_slices, true); }
 hipStream_t plan64_stream(p3d_plan64* p) { return p->stream; }
 void* plan64_work(p3d_plan64* p) { return p->work; }
+bool plan64_shape_ok(int nil, int nxl)
+{
+    return nil >= 1 && nxl >= 1 && nil <= F64_MAX_N && nxl <= F64_MAX_N && p3d::gen_make_plan(nil).nf >= 0 && p3d::gen_make_plan(nxl).nf >= 0;
+}
 
 bool plan64_shear_supported(p3d_plan64* p) { return p->fused && p->mcol && p->mrow && p->st_x != nullptr; }
 bool plan64_engine_shape(int nil, int nxl)

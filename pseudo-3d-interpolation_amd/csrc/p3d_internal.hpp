@@ -80,6 +80,7 @@ int shearlet_col_stats_pair(p3d_plan* plan, int nb, int nsh, const unsigned* sup
 int plan64_create_bare(p3d_plan64** out, int device, int nil, int nxl, int max_slices);
 hipStream_t plan64_stream(p3d_plan64* plan);
 void* plan64_work(p3d_plan64* plan);
+bool plan64_shape_ok(int nil, int nxl);   // a slice shape p3d_plan64_create takes (no device needed)
 // in-place batched fft2 / ifft2 (numpy.fft conventions) of complex128 slices [nslices][nil][nxl] at `buf` (device), enqueued on the plan's
 // stream; slice i is skipped where done[i / done_group] != 0 (done: device, may be NULL)
 int plan64_fft2(p3d_plan64* plan, void* buf, int nslices, bool inverse, const int* done, int done_group);

@@ -1197,21 +1197,18 @@ def _vol_bytes_needed(shape, itemsize, mask_bytes):
     return 8 * n + 2 * itemsize * n + mask_bytes + 3 * slices * plane
 
 
-def pocs_volume(x, mask, niter=50, thresh_op='hard', thresh_model='exponential', eps=1e-9, alpha=1.0, p_max=0.99, p_min=1e-5,
-                sqrt_decay=False, decay_kind='values', version='regular', device=0, results=None):
-    """
-    3-D FFT POCS of ONE volume: ``POCS_algorithm(x, mask, transform=np.fft.fftn, itransform=np.fft.ifftn, transform_kind='FFT', ...)`` of the
-    reference on a ``(n0, n1, n2)`` array (e.g. ``(twt, iline, xline)``) -- the sparse domain couples all three axes, and there is one threshold
-    schedule (from the statistics of ``fftn(x)``), one cost, one iteration count and one early exit for the whole volume.
+def _vol64_bytes_needed(shape, itemsize, mask_bytes):
+    """Device bytes of one ``pocs_volume64`` job: the complex128 work volume (16 B per point), the observed volume and the result, the float64 mask
+    (``mask_bytes``, 8 B per entry), and the 2-D plan's own buffers (up to 256 MiB of complex128 slices, as much again allowed for its records)."""
+    n = int(np.prod(shape, dtype=np.int64))
+    plane = shape[1] * shape[2] * 16
+    slices = max(1, min(shape[0], (256 << 20) // plane))
+    return 16 * n + 2 * itemsize * n + mask_bytes + 2 * slices * plane
 
-    ``x``: complex64 or float32 (float32 runs as complex with a zero imaginary part and returns the real part); ``mask``: ``(n1, n2)``, shared by every
-    ``x[i]``, or ``(n0, n1, n2)``; entries ``<= 1``, weights allowed.  ``n0``: a 7-smooth length from 1 to 1024, ``(n1, n2)``: any slice shape of
-    :func:`pocs_cube`.  hard / soft / garrote; every version; the statistics-driven threshold models.  ``results`` (list, optional) receives one dict
-    with ``niterations``, ``runtime``, ``cost`` and ``costs``.  Returns an array of the shape and dtype of ``x``; an all-zero volume comes back untouched.
 
-    The volume, its result and a complex64 work volume live on the device for the call (``MemoryError`` when they do not fit).
-    """
-    name = 'pocs_volume'
+def _volume_job(name, double, x, mask, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, device, results):
+    """``pocs_volume`` (``double`` False: the float32 kernels) and ``pocs_volume64`` (True: the double-precision loop): the checks, all made before
+    anything reaches the device, the schedule from the statistics of ``fftn(x)`` and the one resident job."""
     x = np.asarray(x)
     if x.ndim != 3:
         raise ValueError(f'{name}: x must be a (n0, n1, n2) volume, got shape {x.shape}')
@@ -1224,11 +1221,15 @@ def pocs_volume(x, mask, niter=50, thresh_op='hard', thresh_model='exponential',
         raise NotImplementedError(f'{name}: the -percentile operators ({thresh_op!r}) are not implemented for volumes (hard, soft, garrote)')
     if thresh_model == 'data-driven':
         raise NotImplementedError(f"{name}: thresh_model='data-driven' is not implemented for volumes")
-    if x.dtype in (np.complex128, np.float64):
-        raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex64 / float32 volumes; there is no double-precision volume loop and '
-                                  'the input is not narrowed silently)')
-    if x.dtype not in (np.complex64, np.float32):
-        raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex64 / float32 volumes)')
+    if double:
+        if x.dtype not in (np.complex128, np.float64, np.complex64, np.float32):
+            raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex128 / float64 / complex64 / float32 volumes)')
+    else:
+        if x.dtype in (np.complex128, np.float64):
+            raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex64 / float32 volumes; the input is not narrowed silently: '
+                                      'pocs_volume64 is the double-precision volume loop)')
+        if x.dtype not in (np.complex64, np.float32):
+            raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex64 / float32 volumes)')
     if version not in _ffi.P3D_VER:
         raise ValueError(f'{name}: unknown POCS version {version!r}')
     if mask.size and np.max(mask) > 1:
@@ -1251,20 +1252,20 @@ def pocs_volume(x, mask, niter=50, thresh_op='hard', thresh_model='exponential',
             results.append({'niterations': 0, 'runtime': 0, 'cost': 0, 'costs': [0]})
         return x.copy()
 
-    maskf = np.ascontiguousarray(mask, dtype=np.float32)
+    maskf = np.ascontiguousarray(mask, dtype=np.float64 if double else np.float32)
     xc = np.ascontiguousarray(x)
-    dt = _ffi.P3D_C64 if np.iscomplexobj(xc) else _ffi.P3D_F32
+    dt = _ffi._PlanBase64._DT[xc.dtype] if double else (_ffi.P3D_C64 if np.iscomplexobj(xc) else _ffi.P3D_F32)
     with _device_lock(device):
-        if not _ffi.shape_supported(n1, n2):
+        if not (_ffi.vol64_shape_supported(n0, n1, n2) if double else _ffi.shape_supported(n1, n2)):
             raise ValueError(f'{name}: slice shape {(n1, n2)} is not covered by the HIP kernels')
-        key = ('vol', n0, n1, n2, device)
+        key = ('vol64' if double else 'vol', n0, n1, n2, device)
         if key not in _plans:
-            needed = _vol_bytes_needed(x.shape, xc.itemsize, maskf.nbytes)
+            needed = (_vol64_bytes_needed if double else _vol_bytes_needed)(x.shape, xc.itemsize, maskf.nbytes)
             free, _ = _ffi.device_mem_info(device)
             if needed > free:
                 raise MemoryError(f'{name}: a {x.shape} {x.dtype} volume needs {needed} bytes on device {device}, {free} are free')
         t0 = time.perf_counter()
-        plan = _cached_plan(key, 1, lambda n: _ffi.VolumePlan(n0, n1, n2, device=device))
+        plan = _cached_plan(key, 1, lambda n: (_ffi.VolumePlan64 if double else _ffi.VolumePlan)(n0, n1, n2, device=device))
         xd, od, md = _batch_buffers(device, xc.nbytes, maskf.nbytes)
         xd.upload(xc)
         md.upload(maskf)
@@ -1279,6 +1280,38 @@ def pocs_volume(x, mask, niter=50, thresh_op='hard', thresh_model='exponential',
     if results is not None:
         results.extend(_result_rows(np.array([done]), sums[:, None], runtime))
     return out
+
+
+def pocs_volume(x, mask, niter=50, thresh_op='hard', thresh_model='exponential', eps=1e-9, alpha=1.0, p_max=0.99, p_min=1e-5,
+                sqrt_decay=False, decay_kind='values', version='regular', device=0, results=None):
+    """
+    3-D FFT POCS of ONE volume: ``POCS_algorithm(x, mask, transform=np.fft.fftn, itransform=np.fft.ifftn, transform_kind='FFT', ...)`` of the
+    reference on a ``(n0, n1, n2)`` array (e.g. ``(twt, iline, xline)``) -- the sparse domain couples all three axes, and there is one threshold
+    schedule (from the statistics of ``fftn(x)``), one cost, one iteration count and one early exit for the whole volume.
+
+    ``x``: complex64 or float32 (float32 runs as complex with a zero imaginary part and returns the real part; complex128 / float64 volumes:
+    :func:`pocs_volume64`); ``mask``: ``(n1, n2)``, shared by every ``x[i]``, or ``(n0, n1, n2)``; entries ``<= 1``, weights allowed.  ``n0``: a 7-smooth length from 1 to 1024, ``(n1, n2)``: any slice shape of
+    :func:`pocs_cube`.  hard / soft / garrote; every version; the statistics-driven threshold models.  ``results`` (list, optional) receives one dict
+    with ``niterations``, ``runtime``, ``cost`` and ``costs``.  Returns an array of the shape and dtype of ``x``; an all-zero volume comes back untouched.
+
+    The volume, its result and a complex64 work volume live on the device for the call (``MemoryError`` when they do not fit).
+    """
+    return _volume_job('pocs_volume', False, x, mask, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, device, results)
+
+
+def pocs_volume64(x, mask, niter=50, thresh_op='hard', thresh_model='exponential', eps=1e-9, alpha=1.0, p_max=0.99, p_min=1e-5,
+                  sqrt_decay=False, decay_kind='values', version='regular', device=0, results=None):
+    """
+    :func:`pocs_volume` in the reference's own precision: the loop runs in complex128 / float64 throughout (POCS.py:566-575, 616), what the reference
+    computes when it is handed a double volume with ``np.fft.fftn`` / ``ifftn``.  Same parameters, defaults, refusals and ``results`` record.
+
+    ``x``: complex128, float64, complex64 or float32 -- always computed in double (the narrow types are widened on load and rounded once on store) and
+    returned in the dtype of ``x``; ``mask`` as for :func:`pocs_volume`, taken as float64.  ``n0``: a 7-smooth length from 1 to 1024; ``n1``, ``n2`` up to
+    5120.  The schedule comes from the double-precision statistics of ``fftn(x)``.
+
+    The volume, its result and a complex128 work volume live on the device for the call (``MemoryError`` when they do not fit).
+    """
+    return _volume_job('pocs_volume64', True, x, mask, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, device, results)
 
 
 # =================================================================================================
