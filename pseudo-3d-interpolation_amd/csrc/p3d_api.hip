@@ -717,7 +717,7 @@ int p3d_host_unregister(void* hptr)
 // ---- internal helpers ---------------------------------------------------------------------------
 // Diagnostic switches of one job: every one selects a slower, equivalent path.  Read once per call of
 // p3d_pocs_run_dev, on the calling thread, and handed down as plain values -- the launch paths never consult the environment.
-struct RunSwitches { bool no_pct_fused; bool no_mask_bits, no_compact, no_real, no_sparse, real_2048, no_resident, no_tstore, force_colpipe, no_colpipe; };
+struct RunSwitches { bool no_pct_fused; bool no_mask_bits, no_compact, no_real, no_sparse, real_2048, no_resident, no_tstore, force_colpipe, no_colpipe, no_tile_screen; };
 static RunSwitches read_switches()
 {
     RunSwitches s;
@@ -731,6 +731,7 @@ static RunSwitches read_switches()
     s.no_tstore = getenv("P3D_NO_TSTORE") != nullptr;
     s.force_colpipe = getenv("P3D_FORCE_COLPIPE") != nullptr;
     s.no_colpipe = getenv("P3D_NO_COLPIPE") != nullptr;
+    s.no_tile_screen = getenv("P3D_NO_TILE_SCREEN") != nullptr;
     return s;
 }
 
@@ -1480,6 +1481,7 @@ static int run_fused(RunJob& j, int nonbinary, unsigned nobs, bool primed_in, co
     const int col_t = is_flex(p->ops_col) ? flex_col_tile(p->nil) : p->ops_col->col_tile;
     if (sparse) {
         c.nzflag = p->nzflag;
+        c.screen = sw.no_tile_screen ? 0 : 1;   // tiles the threshold provably empties end after the first pass of their transform (col_kernel)
         r.zero_off = (unsigned)(wk_slice_stride(p->nil, p->nxl) * (size_t)p->max_slices);
         P3D_TRY(hipMemsetAsync(p->nzcount, 0, sizeof(unsigned long long), p->stream));
     }
@@ -1536,8 +1538,17 @@ static int run_fused(RunJob& j, int nonbinary, unsigned nobs, bool primed_in, co
     unsigned long long* done_sum_d = nullptr;
     if (check_done_rows) P3D_TRY(hipMalloc((void**)&done_sum_d, sizeof(unsigned long long) * nslices));
     struct FreeSum { unsigned long long* p; ~FreeSum() { if (p) hipFree(p); } } free_sum{done_sum_d};
+    // Debug mode of the column pass's empty-tile screen: how many tiles of each iteration it ended, printed when the job is over (one atomic per
+    // such tile and a blocking copy: measurements of the screen's reach and tests only)
+    unsigned* screened_d = nullptr;
+    if (c.screen && getenv("P3D_TILE_SCREEN_COUNT") != nullptr) {
+        P3D_TRY(hipMalloc((void**)&screened_d, sizeof(unsigned) * niter));
+        P3D_TRY(hipMemsetAsync(screened_d, 0, sizeof(unsigned) * niter, p->stream));
+    }
+    struct FreeCount { unsigned* p; ~FreeCount() { if (p) hipFree(p); } } free_count{screened_d};
     for (int k = 0; k < niter; ++k) {
         c.iter = k;
+        c.screened = screened_d ? screened_d + k : nullptr;
         if (percentile) {
             // forward column transform | rank |X|, tau_k = the interpolated order statistic, threshold | inverse column transform
             const size_t per_slice = p->slice_elems();
@@ -1645,6 +1656,12 @@ static int run_fused(RunJob& j, int nonbinary, unsigned nobs, bool primed_in, co
     unsigned long long kept_blocks = 0;
     if (sparse) P3D_TRY(hipMemcpyAsync(&kept_blocks, p->nzcount, sizeof kept_blocks, hipMemcpyDeviceToHost, p->stream));
     if ((rc = j.frame.collect(j.niter_done, j.elapsed_ms))) return rc;
+    if (screened_d) {
+        std::vector<unsigned> screened_h(niter);
+        P3D_TRY(hipMemcpy(screened_h.data(), screened_d, sizeof(unsigned) * niter, hipMemcpyDeviceToHost));
+        for (int k = 0; k < niter; ++k)
+            fprintf(stderr, "p3d tile screen: iteration %d: %u of %ld tiles ended after the first pass of their transform\n", k, screened_h[k], (long)tiles_work * nslices);
+    }
     if (sparse) p->last_nonzero_fraction = (double)kept_blocks / ((double)niter * nslices * (real_path ? (n2_work + 7) / 8 : nblocks));
     if (profile) {
         p->prof_col_ms = p->prof_row_ms = 0;

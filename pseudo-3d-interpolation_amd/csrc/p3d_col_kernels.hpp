@@ -14,6 +14,15 @@ __device__ __forceinline__ bool lex_greater(float ar, float ai, float br, float 
     return (ar > br) || (ar == br && ai > bi);
 }
 
+// sum of x over the 8 lanes of a wavefront that share lane & 7 (all of them get it): lane ^ 8 inside a row of 16 lanes, then across the rows
+__device__ __forceinline__ float lanes8_sum(float x)
+{
+    x += __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), 0x128 /* row_ror:8 */, 0xf, 0xf, false));
+    x += __shfl_xor(x, 16, 64);
+    x += __shfl_xor(x, 32, 64);
+    return x;
+}
+
 // T columns per workgroup; CW = min(T, 8) of them share a 64-byte column block.
 template <int N, int T, int MODE>
 __global__ __launch_bounds__(T* Plan<N>::TPL, (T * Plan<N>::TPL >= 1024 ? 4 : P3D_WAVES_PER_EU)) void col_kernel(const ColArgs a)
@@ -49,11 +58,17 @@ __global__ __launch_bounds__(T* Plan<N>::TPL, (T * Plan<N>::TPL >= 1024 ? 4 : P3
 
     if (a.done && a.done[slice] != 0) return;
 
-    for (int i = tid; i < ColTables<N>::slots(); i += THREADS) twl[i] = a.tw[i];
-    __syncthreads();
+    constexpr bool ITER = MODE == COL_ITER || MODE == COL_ITER_SOFT || MODE == COL_ITER_GARROTE;
+    // (the kernel with the empty-tile screen copies its tables after the screen: the first pass needs none, and most tiles end there.  The split
+    // transform and the late copy are the kernel's one code path -- the same operations on the same operands as before, so the same bits -- and are
+    // NOT behind P3D_NO_TILE_SCREEN: the switch, ColArgs::screen, takes out the bound and the early return alone)
+    constexpr bool SCREENED = ITER && N == 1024 && T == 8;
+    if constexpr (!SCREENED) {
+        for (int i = tid; i < ColTables<N>::slots(); i += THREADS) twl[i] = a.tw[i];
+        __syncthreads();
+    }
 
     const LDS lds{data + cbl * LDS::stride(N) + c_lo};
-    constexpr bool ITER = MODE == COL_ITER || MODE == COL_ITER_SOFT || MODE == COL_ITER_GARROTE;
     const int vcol = valid ? col : 0;
     // wave-uniform slice bases + 32-bit element offsets (see row_kernel)
     const c32* const inb = a.in + (size_t)slice * (a.in_std ? (size_t)N * a.n2 : wk_slice_stride(N, a.n2));
@@ -102,7 +117,36 @@ __global__ __launch_bounds__(T* Plan<N>::TPL, (T * Plan<N>::TPL >= 1024 ? 4 : P3
     for (int q = 0; q < PPT; ++q)   // scalar base + 32-bit byte offset (a slice is far below 4 GiB); columns past the edge re-read column 0
         v[q] = *reinterpret_cast<const c32*>(reinterpret_cast<const char*>(inb) + (in_org + (unsigned)(tl + TPL * q) * in_pitch) * 8u);
 
-    if (MODE != COL_INV) line_fft<N, FWD, false>(v, lds, tw, tl);
+    if constexpr (SCREENED) {
+        // Nearly every tile of a sparse spectrum (96 % on the headline cube) is transformed only to find that the threshold leaves nothing of
+        // it.  Most of them can be told after the first, in-register pass (p3d_tile_screen.hpp): no exchange through LDS, no later pass,
+        // and the tile ends as it would have ended -- flag cleared, nothing stored.  A tile the bound does not settle goes on from the
+        // values it has, so every bit of the result stays what it was.
+        line_fft_first<N, FWD>(v, tw, tl);
+        if (a.screen && a.nzflag != nullptr) {
+            const int op = MODE == COL_ITER ? 0 : (MODE == COL_ITER_SOFT ? 1 : 2);
+            const float thr = screen_threshold(a.tau[(size_t)slice * a.niter + a.iter], op);
+            // this thread's term, summed over the 8 threads of the column in this wavefront (lane = c_lo + 8 * (tl & 7)) ...
+            const float part = lanes8_sum(screen_term(v));
+            float* const red = reinterpret_cast<float*>(data);   // (free until the first exchange, which starts with a barrier)
+            if ((tid & 63) < 8) red[(tid >> 6) * 8 + (tid & 7)] = part;
+            __syncthreads();
+            // ... and over the 8 wavefronts: every wavefront adds the same 64 partial sums in the same order, so lane l of each holds
+            // the very same U of column l & 7, and the answer is the same in the whole workgroup
+            const float u = lanes8_sum(red[tid & 63]);
+            if (!__any(!screen_proves_empty(u, thr))) {
+                if (tid == 0) {
+                    a.nzflag[(size_t)slice * gridDim.x + tile] = 0;
+                    if (a.screened != nullptr) atomicAdd(a.screened, 1u);
+                }
+                return;
+            }
+        }
+        for (int i = tid; i < ColTables<N>::slots(); i += THREADS) twl[i] = a.tw[i];   // (read behind the two barriers of the first exchange)
+        line_fft_rest<N, FWD, false>(v, lds, tw, tl);
+    } else if (MODE != COL_INV) {
+        line_fft<N, FWD, false>(v, lds, tw, tl);
+    }
 
     if (ITER || (MODE == COL_FWD && a.tau != nullptr)) {
         const c32 tau = a.tau[(size_t)slice * a.niter + a.iter];

@@ -458,6 +458,25 @@ struct PassLoop {
     }
 };
 
+// The transform in two halves, for a caller that looks at the values between them: the first pass, which needs neither LDS nor
+// twiddles -- register k of thread tl then holds DFT_R over q of element tl + TPL*q, output digit_rev<R>(k) (R = radix(DIR, 0)) --
+// and everything after it.
+template <int N, int DIR, class TW>
+P3D_D void line_fft_first(c32 (&v)[Plan<N>::PPT], TW tw, int tl)
+{
+    pass_compute<N, DIR, 0>(v, tw, tl);
+}
+template <int N, int DIR, bool WAVE, class LDS, class TW>
+P3D_D void line_fft_rest(c32 (&v)[Plan<N>::PPT], LDS lds, TW tw, int tl)
+{
+    if constexpr (Plan<N>::NPASS > 1) {
+        exchange_sync<WAVE>();  // everybody is done reading the previous contents
+        pass_scatter<N, DIR, 0>(v, lds, tl);
+        exchange_sync<WAVE>();
+        PassLoop<N, DIR, 1, WAVE, LDS, TW>::run(v, lds, tw, tl);
+    }
+}
+
 // Transform one line held in canonical register layout; result is canonical again.
 // Every thread of the workgroup (WAVE = false) / wavefront (WAVE = true) must call this.
 template <int N, int DIR, bool WAVE, class LDS, class TW>

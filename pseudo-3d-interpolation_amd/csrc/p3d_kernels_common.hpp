@@ -6,6 +6,7 @@
 
 #include "p3d_fft.hpp"
 #include "p3d_shrink.hpp"
+#include "p3d_tile_screen.hpp"
 
 // build-time knobs for experiments (tools/build_variant.sh)
 #ifndef P3D_ROW_THREADS
@@ -221,6 +222,9 @@ struct ColArgs {
     int herm_n2;        // COL_STATS on the half-spectrum work buffer of a float32 cube (columns 0 ... herm_n2/2 of herm_n2): the statistics
                         // of the WHOLE Hermitian spectrum -- a column with a mirror image counts twice and offers its conjugates to the
                         // lexicographic maximum (0: plain)
+    int screen;         // COL_ITER* of 8-column tiles of 1024 points: end a tile after the first pass of its transform when the bound of
+                        // p3d_tile_screen.hpp proves that the threshold empties it (needs nzflag; off: P3D_NO_TILE_SCREEN=1)
+    unsigned* screened; // debug runs (P3D_TILE_SCREEN_COUNT=1): counts the tiles of this launch that ended there; nullptr otherwise
 };
 
 // |x| for the cost sums: the hardware square root (1 ulp) without the IEEE fix-up sequence the library call expands to (8 more
