@@ -793,6 +793,40 @@ int p3d_vol64_run_dev(p3d_vol64_plan* vplan, const void* x_dev, int dtype, const
 int p3d_vol64_run(p3d_vol64_plan* vplan, const void* x_host, int dtype, const double* mask_host, const double* tau, const p3d_pocs_params* params, void* out_host,
                   int32_t* niter_done, double* sums, double* elapsed_ms);
 
+/* ---- 3-D DCT POCS: a whole volume as ONE job with the cosine transform (csrc/p3d_vol_dct.hip) ---------------------------------------------------
+ * POCS_algorithm(x, mask, transform=partial(scipy.fft.dctn, norm=...), itransform=partial(scipy.fft.idctn, norm=...), transform_kind='DCT', ...) on a
+ * volume x of (n0, n1, n2) points, C-contiguous, n2 fastest: the type-2 DCT over all three axes, one schedule, one cost, one iteration count and one
+ * early exit for the volume.  norm: P3D_DCT_BACKWARD / P3D_DCT_ORTHO, the `norm` keyword of both callables.  Per iteration on a complex64 work volume in
+ * the reordered sample order of the DCT along axes 1 and 2: the fft2 passes of a p3d_plan for (n1, n2) slices, the group pass of the 2-D DCT loop
+ * (combine), one kernel that transforms a tile of plane positions along axis 0 -- the reordering of axis 0 folded into its loads and stores --, combines,
+ * thresholds, splits and transforms back (the 3-D cosine spectrum never goes to memory), the group pass again (split), the ifft2 passes, and the
+ * re-insertion with cost sums folded in a fixed order (results are bitwise repeatable).  float32 kernels: complex64 volumes, or float32 ones, which run as
+ * complex with a zero imaginary part and return the real part.
+ *   shape_supported  1 when n0 is a 7-smooth length from 1 to 1024 (n0 = 1: the axis-0 pass is its group step alone) and p3d_shape_supported(n1, n2)
+ *   create   `plan`: a p3d_plan for (n1, n2) slices on `device` to borrow (not owned: it must outlive the volume plan, which runs on its stream
+ *            and is as little re-entrant), or NULL: the volume plan creates and owns one.  Allocates the complex64 work volume and the DCT tables of all
+ *            three axes for both norms.  P3D_ERR_UNSUPPORTED for any other n0 or slice shape
+ *   dct3     scipy.fft.dctn (inverse = 0) / idctn (inverse = 1) of one complex64 volume through the loop's own passes (test hook); in == out is allowed
+ *   shrink   threshold(dctn(x), tau, thresh_op), tau HOST [2] doubles (Re, Im): the keep / zero decision of every coefficient (test hook)
+ *   stats    stats_host [P3D_STATS_PER_SLICE] of X0 = dctn(x), the layout of p3d_pocs_stats for ONE volume
+ *   run      the loop, every argument as p3d_vol_run takes it (dtypes, the mask and P3D_FLAG_MASK_PER_SLICE, tau, niter_done, sums, elapsed_ms, hard / soft /
+ *            garrote, versions, eps, alpha, P3D_FLAG_PROFILE read with p3d_voldct_last_profile, the all-zero volume, an `out` that overlaps `x`).
+ * The *_dev entries take DEVICE pointers for x, mask and out, the others HOST pointers (staged through volumes the plan allocates on first use). */
+typedef struct p3d_voldct_plan p3d_voldct_plan;
+int p3d_voldct_shape_supported(int n0, int n1, int n2);
+int p3d_voldct_plan_create(p3d_voldct_plan** out, int device, int n0, int n1, int n2, p3d_plan* plan);
+int p3d_voldct_plan_destroy(p3d_voldct_plan* vplan);
+int p3d_voldct_dct3_c64_dev(p3d_voldct_plan* vplan, const void* in_dev, void* out_dev, int norm, int inverse);
+int p3d_voldct_dct3_c64(p3d_voldct_plan* vplan, const void* in_host, void* out_host, int norm, int inverse);
+int p3d_voldct_shrink_c64(p3d_voldct_plan* vplan, const void* in_host, const double* tau, int thresh_op, int norm, void* out_host);
+int p3d_voldct_last_profile(p3d_voldct_plan* vplan, double* zpass_ms, int* zpass_launches);
+int p3d_voldct_stats_dev(p3d_voldct_plan* vplan, const void* x_dev, int dtype, int norm, double* stats_host);
+int p3d_voldct_stats(p3d_voldct_plan* vplan, const void* x_host, int dtype, int norm, double* stats_host);
+int p3d_voldct_run_dev(p3d_voldct_plan* vplan, const void* x_dev, int dtype, const float* mask_dev, const double* tau, const p3d_pocs_params* params, int norm,
+                       void* out_dev, int32_t* niter_done, double* sums, double* elapsed_ms);
+int p3d_voldct_run(p3d_voldct_plan* vplan, const void* x_host, int dtype, const float* mask_host, const double* tau, const p3d_pocs_params* params, int norm,
+                   void* out_host, int32_t* niter_done, double* sums, double* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

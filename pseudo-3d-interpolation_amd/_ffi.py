@@ -251,6 +251,19 @@ PROTOTYPES = {
                                     C.POINTER(C.c_double)]),
     "p3d_vol64_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.POINTER(C.c_double)]),
+    "p3d_voldct_shape_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "p3d_voldct_plan_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_voldct_plan_destroy": (C.c_int, [C.c_void_p]),
+    "p3d_voldct_dct3_c64_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "p3d_voldct_dct3_c64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "p3d_voldct_shrink_c64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_voldct_last_profile": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "p3d_voldct_stats_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_voldct_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "p3d_voldct_run_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_double)]),
+    "p3d_voldct_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(PocsParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(C.c_double)]),
 }
 
 
@@ -1031,6 +1044,81 @@ class VolumePlan(_PlanBase):
         ms, n = C.c_double(), C.c_int()
         check(self._c("last_profile")(self.handle, C.byref(ms), C.byref(n)))
         return {"zpass_ms": ms.value, "zpass_launches": n.value}
+
+
+def voldct_shape_supported(n0, n1, n2):
+    return bool(lib().p3d_voldct_shape_supported(int(n0), int(n1), int(n2)))
+
+
+class VolumePlanDct(VolumePlan):
+    """p3d_voldct_plan wrapper: 3-D DCT POCS of one ``(n0, n1, n2)`` volume (csrc/p3d_vol_dct.hip), scipy.fft.dctn / idctn (type 2) over all three axes.
+    The methods of :class:`VolumePlan` with a ``norm`` keyword (None / 'backward' / 'ortho'); the transform hook is `dct3`.  ``plan``: a :class:`Plan` for
+    ``(n1, n2)`` slices to borrow, or None."""
+    _DESTROY = "p3d_voldct_plan_destroy"
+    _ENTRY, _HOOK = "p3d_voldct_", "c64"
+
+    def dct3(self, x, inverse=False, norm=None):
+        """scipy.fft.dctn (``inverse``: idctn) of a complex64 volume through the loop's own passes."""
+        xc, _ = self._volume(x, complex_only=True)
+        out = np.empty_like(xc)
+        check(self._c("dct3_c64")(self.handle, _ptr(xc), _ptr(out), Plan._dct_norm(norm), int(bool(inverse))))
+        return out
+
+    def dct3_dev(self, in_ptr, out_ptr, inverse=False, norm=None):
+        check(self._c("dct3_c64_dev")(self.handle, C.c_void_p(in_ptr), C.c_void_p(out_ptr), Plan._dct_norm(norm), int(bool(inverse))))
+
+    def fft3(self, *args, **kwargs):
+        """Not part of this plan: there is no ``p3d_voldct_fft3_*`` entry."""
+        raise UnsupportedError(P3D_ERR_UNSUPPORTED, "VolumePlanDct has no fft3 / fft3_dev: its transform hooks are dct3 / dct3_dev")
+
+    fft3_dev = fft3
+
+    def shrink(self, x, tau, thresh_op="hard", norm=None):
+        """threshold(dctn(x), tau, kind) on the device: the keep / zero decision of every coefficient."""
+        xc, _ = self._volume(x, complex_only=True)
+        t = _tau_table(tau, ())
+        out = np.empty_like(xc)
+        check(self._c("shrink_c64")(self.handle, _ptr(xc), _ptr(t), P3D_OP[thresh_op], Plan._dct_norm(norm), _ptr(out)))
+        return out
+
+    def stats(self, x, norm=None):
+        """The six statistics of ``dctn(x)`` as a (1, 6) array (one row: the volume), the layout ``_schedule_from_stats`` takes."""
+        xc, dt = self._volume(x)
+        st = np.empty((1, STATS_PER_SLICE), np.float64)
+        check(self._c("stats")(self.handle, _ptr(xc), dt, Plan._dct_norm(norm), _ptr(st)))
+        return st
+
+    def stats_dev(self, x_ptr, dtype, norm=None):
+        st = np.empty((1, STATS_PER_SLICE), np.float64)
+        check(self._c("stats_dev")(self.handle, C.c_void_p(x_ptr), int(dtype), Plan._dct_norm(norm), _ptr(st)))
+        return st
+
+    def _run(self, entry, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, thresh_op, version, eps, alpha, mask_per_slice, profile=False, norm=None):
+        t = _tau_table(tau, (int(niter),))
+        prm = Plan._params(niter, thresh_op, version, eps, alpha, profile, False, mask_per_slice)
+        if prm.thresh_op & P3D_OP_PERCENTILE:
+            raise UnsupportedError(P3D_ERR_UNSUPPORTED, f"thresh_op {thresh_op!r} is not implemented for volumes")
+        done = np.zeros(1, np.int32)
+        sums = np.zeros(int(niter) + 1, np.float64)
+        ms = C.c_double(0.0)
+        check(self._c(entry)(self.handle, C.c_void_p(x_ptr), int(dtype), C.c_void_p(mask_ptr), _ptr(t), C.byref(prm), Plan._dct_norm(norm), C.c_void_p(out_ptr),
+                             _ptr(done), _ptr(sums), C.byref(ms)))
+        return int(done[0]), sums, ms.value
+
+    def run(self, x, mask, tau, niter, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, norm=None):
+        """`VolumePlan.run` with the DCT pair of ``norm``; ``tau``: the schedule of ``dctn(x)``."""
+        xc, dt = self._volume(x)
+        m = np.ascontiguousarray(mask, dtype=self._MASK_DT)
+        if m.shape != self.shape[1:] and m.shape != self.shape:
+            raise ValueError(f"mask shape {m.shape} is neither {self.shape[1:]} nor {self.shape}")
+        out = np.empty_like(xc)
+        done, sums, ms = self._run("run", xc.ctypes.data, dt, m.ctypes.data, tau, niter, out.ctypes.data, thresh_op, version, eps, alpha, m.ndim == 3, norm=norm)
+        return out, done, sums, ms
+
+    def run_dev(self, x_ptr, dtype, mask_ptr, tau, niter, out_ptr, thresh_op="hard", version="regular", eps=0.0, alpha=1.0, mask_per_slice=False,
+                profile=False, norm=None):
+        """`VolumePlan.run_dev` with the DCT pair of ``norm``."""
+        return self._run("run_dev", x_ptr, dtype, mask_ptr, tau, niter, out_ptr, thresh_op, version, eps, alpha, mask_per_slice, profile, norm)
 
 
 def vol64_shape_supported(n0, n1, n2):

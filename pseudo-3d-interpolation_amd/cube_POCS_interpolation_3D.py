@@ -14,7 +14,8 @@ Optional ``patch_shape`` / ``patch_overlap`` / ``patch_taper`` keys of the ``met
 ``_patch-<w_il>x<w_xl>`` to the output prefix.  Optional ``volume: true`` in the ``metadata`` block (an extension as well): the data variable, ``dim``
 first, runs as ONE 3-D FFT POCS job (``pocs_volume``: np.fft.fftn / ifftn over all three axes, one schedule and one early exit for the volume) with the fold mask or
 ``mask_var`` (2-D, or 3-D with the data variable's dims); the prefix gains ``_vol`` and the runtime file holds one line.  ``volume: reference`` runs the same job in the
-reference's double precision (``pocs_volume64``), whatever the data variable's dtype; the prefix gains ``_vol64``.
+reference's double precision (``pocs_volume64``), whatever the data variable's dtype; the prefix gains ``_vol64``.  ``volume: dct`` (with ``transform_kind: dct``
+and the optional ``dct_norm``) runs the volume as ONE 3-D DCT POCS job (``pocs_volume_dct``: scipy.fft.dctn / idctn over all three axes); the prefix gains ``_vol``.
 """
 import argparse
 import datetime
@@ -27,7 +28,7 @@ import numpy as np
 import yaml
 
 from .cube_io import open_cube, save_cube
-from .functions.POCS import APOCS, FPOCS, POCS, pocs_cube, pocs_volume, pocs_volume64  # noqa: F401
+from .functions.POCS import APOCS, FPOCS, POCS, pocs_cube, pocs_volume, pocs_volume64, pocs_volume_dct  # noqa: F401
 from .functions.utils import xprint
 
 POCS_VERSIONS = {'POCS': POCS, 'FPOCS': FPOCS, 'APOCS': APOCS}
@@ -94,15 +95,22 @@ def dct_norm_from_metadata(metadata):
 
 def volume_from_metadata(metadata):
     """The optional ``volume`` key of the YAML ``metadata`` block (3-D FFT POCS of the whole data variable as one job) and the combinations it excludes:
-    False, True (``pocs_volume``, the float32 kernels) or ``'reference'`` (``pocs_volume64``, the loop in double precision)."""
+    False, True (``pocs_volume``, the float32 kernels), ``'reference'`` (``pocs_volume64``, the loop in double precision) or ``'dct'`` (``pocs_volume_dct``, the
+    3-D cosine transform, which goes with ``transform_kind: dct`` only)."""
     volume = metadata.get('volume')
     if volume is None or volume is False:
         return False
-    if volume is not True and volume != 'reference':
-        raise ValueError(f'volume must be true, false or reference, got {volume!r}')
-    key = 'volume: true' if volume is True else 'volume: reference'
+    if volume is not True and volume != 'reference' and volume != 'dct':
+        raise ValueError(f'volume must be true, false, reference or dct, got {volume!r}')
+    key = 'volume: true' if volume is True else f'volume: {volume}'
     if metadata.get('patch_shape') is not None:
         raise NotImplementedError(f'{key} cannot be combined with patch_shape (3-D windows are not implemented)')
+    if volume == 'dct':
+        if str(metadata['transform_kind']).upper() != 'DCT':
+            raise NotImplementedError(f"{key} is the 3-D cosine transform and goes with transform_kind DCT only, got {metadata['transform_kind']}")
+        if metadata.get('precision') == 'reference':
+            raise NotImplementedError(f'{key} cannot be combined with precision: reference (a double-precision DCT volume loop is not implemented)')
+        return volume
     if str(metadata['transform_kind']).upper() != 'FFT':
         raise NotImplementedError(f"{key} is implemented for transform_kind FFT only, got {metadata['transform_kind']}")
     if volume is True and metadata.get('precision') == 'reference':
@@ -184,7 +192,7 @@ def main(argv=sys.argv, return_dataset=False):
         w = metadata['patch_shape']
         w_il, w_xl = (int(w), int(w)) if np.ndim(w) == 0 else (int(w[0]), int(w[1]))
         prefix += f'_patch-{w_il}x{w_xl}'
-    if VOLUME:                                               # an extension: the whole data variable as one 3-D FFT POCS job
+    if VOLUME:                                               # an extension: the whole data variable as one 3-D FFT (or DCT) POCS job
         prefix += '_vol64' if VOLUME == 'reference' else '_vol'
 
     coord = np.asarray(cube.coords[dim])
@@ -241,7 +249,7 @@ def main(argv=sys.argv, return_dataset=False):
         groups.append(cur)
     if VOLUME:
         results = []
-        run_volume = pocs_volume64 if VOLUME == 'reference' else pocs_volume
+        run_volume = pocs_volume64 if VOLUME == 'reference' else partial(pocs_volume_dct, dct_norm=metadata['dct_norm']) if VOLUME == 'dct' else pocs_volume
         merged[...] = run_volume(data, mask, results=results, **{k: kwargs[k] for k in VOLUME_KEYS if k in kwargs})
         for sl in batches:                                   # the output keeps its unit, one file per batch; the job has ONE runtime record
             save_cube(wrap(merged[sl], sl), create_file_path(coord[sl], prefix=prefix, root_path=out_path, suffix=suffix))

@@ -1206,9 +1206,13 @@ def _vol64_bytes_needed(shape, itemsize, mask_bytes):
     return 16 * n + 2 * itemsize * n + mask_bytes + 2 * slices * plane
 
 
-def _volume_job(name, double, x, mask, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, device, results):
-    """``pocs_volume`` (``double`` False: the float32 kernels) and ``pocs_volume64`` (True: the double-precision loop): the checks, all made before
-    anything reaches the device, the schedule from the statistics of ``fftn(x)`` and the one resident job."""
+def _volume_job(name, double, x, mask, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, device, results, dct=False,
+                dct_norm=None):
+    """``pocs_volume`` (``double`` False: the float32 kernels), ``pocs_volume64`` (True: the double-precision loop) and ``pocs_volume_dct`` (``dct``: the
+    float32 kernels with the cosine transform of norm ``dct_norm``): the checks, all made before anything reaches the device, the schedule from the
+    statistics of ``fftn(x)`` (``dctn(x)``) and the one resident job."""
+    if dct:
+        dct_norm = _dct_norm(None, dct_norm)
     x = np.asarray(x)
     if x.ndim != 3:
         raise ValueError(f'{name}: x must be a (n0, n1, n2) volume, got shape {x.shape}')
@@ -1225,9 +1229,9 @@ def _volume_job(name, double, x, mask, niter, thresh_op, thresh_model, eps, alph
         if x.dtype not in (np.complex128, np.float64, np.complex64, np.float32):
             raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex128 / float64 / complex64 / float32 volumes)')
     else:
-        if x.dtype in (np.complex128, np.float64):
-            raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex64 / float32 volumes; the input is not narrowed silently: '
-                                      'pocs_volume64 is the double-precision volume loop)')
+        if x.dtype in (np.complex128, np.float64):   # refused either way; only the pointer to a double-precision loop differs
+            hint = 'there is no double-precision DCT volume loop' if dct else 'pocs_volume64 is the double-precision volume loop'
+            raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex64 / float32 volumes; the input is not narrowed silently: {hint})')
         if x.dtype not in (np.complex64, np.float32):
             raise NotImplementedError(f'{name}: {x.dtype} input is not implemented (complex64 / float32 volumes)')
     if version not in _ffi.P3D_VER:
@@ -1258,23 +1262,26 @@ def _volume_job(name, double, x, mask, niter, thresh_op, thresh_model, eps, alph
     with _device_lock(device):
         if not (_ffi.vol64_shape_supported(n0, n1, n2) if double else _ffi.shape_supported(n1, n2)):
             raise ValueError(f'{name}: slice shape {(n1, n2)} is not covered by the HIP kernels')
-        key = ('vol64' if double else 'vol', n0, n1, n2, device)
+        key = ('vol64' if double else 'voldct' if dct else 'vol', n0, n1, n2, device)
         if key not in _plans:
             needed = (_vol64_bytes_needed if double else _vol_bytes_needed)(x.shape, xc.itemsize, maskf.nbytes)
             free, _ = _ffi.device_mem_info(device)
             if needed > free:
                 raise MemoryError(f'{name}: a {x.shape} {x.dtype} volume needs {needed} bytes on device {device}, {free} are free')
         t0 = time.perf_counter()
-        plan = _cached_plan(key, 1, lambda n: (_ffi.VolumePlan64 if double else _ffi.VolumePlan)(n0, n1, n2, device=device))
+        plan = _cached_plan(key, 1, lambda n: (_ffi.VolumePlan64 if double else _ffi.VolumePlanDct if dct else _ffi.VolumePlan)(n0, n1, n2, device=device))
+        norm = dict(norm=dct_norm) if dct else {}
         xd, od, md = _batch_buffers(device, xc.nbytes, maskf.nbytes)
         xd.upload(xc)
         md.upload(maskf)
-        stats = plan.stats_dev(xd.ptr, dt)
+        stats = plan.stats_dev(xd.ptr, dt, **norm)
+        if dct and dt == _ffi.P3D_F32:
+            stats[:, 1] = 0.0  # the DCT of a real volume is real (the complex kernels leave rounding noise in the imaginary part): a real schedule
         tau = _schedule_from_stats(stats, x.size, thresh_model, niter, p_max, p_min, decay_kind)[0]
         if sqrt_decay:
             tau = np.sqrt(tau)   # POCS.py:595
         done, sums, _ = plan.run_dev(xd.ptr, dt, md.ptr, tau, niter, od.ptr, thresh_op=thresh_op, version=version, eps=eps, alpha=alpha,
-                                     mask_per_slice=maskf.ndim == 3)
+                                     mask_per_slice=maskf.ndim == 3, **norm)
         out = od.download(xc.shape, xc.dtype)
         runtime = time.perf_counter() - t0
     if results is not None:
@@ -1312,6 +1319,23 @@ def pocs_volume64(x, mask, niter=50, thresh_op='hard', thresh_model='exponential
     The volume, its result and a complex128 work volume live on the device for the call (``MemoryError`` when they do not fit).
     """
     return _volume_job('pocs_volume64', True, x, mask, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, device, results)
+
+
+def pocs_volume_dct(x, mask, niter=50, thresh_op='hard', thresh_model='exponential', eps=1e-9, alpha=1.0, p_max=0.99, p_min=1e-5,
+                    sqrt_decay=False, decay_kind='values', version='regular', device=0, results=None, dct_norm=None):
+    """
+    3-D DCT POCS of ONE volume: ``POCS_algorithm(x, mask, transform=partial(scipy.fft.dctn, norm=dct_norm), itransform=partial(scipy.fft.idctn,
+    norm=dct_norm), transform_kind='DCT', ...)`` of the reference on a ``(n0, n1, n2)`` array -- the type-2 cosine transform over all three axes, whose even
+    extension wraps no energy around the edges of the volume (along ``twt`` the first and last samples have nothing in common).  One threshold schedule
+    (from the statistics of ``dctn(x)``; real for a float32 volume; ``p_min='adaptive'`` is allowed), one cost, one iteration count and one early exit.
+
+    Parameters, defaults, refusals and the ``results`` record of :func:`pocs_volume`; ``dct_norm``: ``None`` / ``'backward'`` (SciPy's default) or ``'ortho'``,
+    the ``norm`` of both callables.  ``x``: complex64 or float32 (float32 runs as complex with a zero imaginary part and returns the real part).
+
+    The volume, its result and a complex64 work volume live on the device for the call (``MemoryError`` when they do not fit).
+    """
+    return _volume_job('pocs_volume_dct', False, x, mask, niter, thresh_op, thresh_model, eps, alpha, p_max, p_min, sqrt_decay, decay_kind, version, device, results,
+                       dct=True, dct_norm=dct_norm)
 
 
 # =================================================================================================
